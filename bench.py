@@ -33,6 +33,10 @@ The JSON line also carries
                   rates on a bounded sample, reported SEPARATELY -- never part of `value`.
     cpu_baseline  the CPU oracle (numpy/scipy restatement of DSP.jl's algorithm; kind "port") timed on a bounded sample: 1 thread
                   (`value`), all cores (`multi`), and the line-faithful per-block loop (`faithful`).
+
+--dump-outputs DIR writes what the last timed step computed on rank 0 -- filt.npy, welch_power.npy, welch_mean.npy / stft.npy / resample.npy,
+resample_avg.npy -- with a fixed, seeded sample of the outputs too large for 64 MB.  The inputs are seeded, so the same arguments give the same
+inputs on every run and two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -69,7 +73,13 @@ def parse():
     ap.add_argument("--no-live-pmc", action="store_true", help="do not re-run under rocprofv3 for roofline.traffic")
     ap.add_argument("--describe-rows", action="store_true", help="print what every row of `kernels` runs (ROW_INFO) and exit")
     ap.add_argument("--dry", action="store_true", help="CPU dry mode (tests): gloo, no device work; exercises sharding, the collective and the JSON schema")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last step computed as DIR/<name>.npy (float32; a fixed, seeded sample of "
+                         "outputs larger than the 64 MB budget) so that two builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def lowpass_taps(n):
@@ -311,6 +321,30 @@ ROW_INFO = {
     "conv2d": ("d.conv(A, B): mdsp_convnd_fft", "4096 x 4096 Float32 with a 33 x 33 kernel", "4 in + 4 out"),
     "filtfilt": ("d.filtfilt(b, x) through the host mirror", "256 taps, 2^26 Float32", "8"),
 }
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: budget of all files together
+
+
+def sample(t, dim, k, seed=1776):
+    """A fixed, seeded sample of k indices of t along `dim` (in index order); t itself when it has no more than k."""
+    import numpy as np
+    import torch
+    if t.shape[dim] <= k:
+        return t
+    idx = np.sort(np.random.default_rng(seed).choice(t.shape[dim], k, replace=False))
+    return t.index_select(dim, torch.from_numpy(idx).to(t.device))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: the arrays of the last timed step as <path>/<name>.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: t.detach().cpu().numpy() for name, t in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def spread(tm):
@@ -848,6 +882,7 @@ def main():
                 dist.all_reduce(mean, op=dist.ReduceOp.SUM)
                 mean.mul_(1.0 / world)
         coll = lambda: (psd.sum(0, dtype=torch.float64), mean, float(world))     # (this rank's contribution, the collective's result, divisor)
+        outs = lambda: {"filt": sample(y, 0, 1 << 22), "welch_power": psd[0], "welch_mean": mean}              # 16 MB of the 4 GiB filter output
         names = ("filt", "welch")
         alg = (8.0 * n, 4.0 * n)
         kern = ("ols_fused_kernel (overlap-save filt, 8 B/sample)", "mdsp_welch_w64c_asm + reduce + finalize (4 B/sample)")
@@ -871,6 +906,7 @@ def main():
             tm.rec(b_)
             tm.rec(c)                            # channels are independent: no collective on this path
         coll = None
+        outs = lambda: {"stft": torch.view_as_real(sample(out.view(nch * K, 1024), 0, 4096))}   # 4096 whole frames (32 MB) as (frame, bin, re / im)
         names = ("stft", "none")
         alg = (40.0 * n * nch, 0.0)
         kern = ("stft_fused_kernel (config 4: 8 + 8*1024/256 = 40 B/sample)", "-")
@@ -908,6 +944,7 @@ def main():
             avg.mul_(1.0 / (nch * world))
             tm.rec(c)
         coll = lambda: (y[:, ol.value - TAIL:].sum(0, dtype=torch.float64), avg, float(nch * world))
+        outs = lambda: {"resample": sample(y, 1, 1 << 21), "resample_avg": avg}                                  # the same 2^21 output indices of every channel (32 MB)
         names = ("resample", "channel average + all-reduce")
         alg = ((4 + 4 * 160 / 147) * n * nch, 0.0)
         kern = ("polyphase_mfma_kernel (config 5: 4 + 4*160/147 = 8.354 B/input sample)", "-")
@@ -939,6 +976,8 @@ def main():
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    if args.dump_outputs and rank == 0:                           # before the yardsticks below reuse the step's buffers
+        dump_outputs(args.dump_outputs, outs())
 
     # self-check of the step's collective (outside the timed region): every rank's contribution is gathered over a DIFFERENT transport
     # (torch.distributed all_gather), summed in Float64 on each rank, and compared with what the step's own all-reduce left behind
