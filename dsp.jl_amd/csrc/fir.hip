@@ -1483,6 +1483,8 @@ template <typename XS, typename A, typename R> int fir_launch(mdsp_fir_s* f, Fir
         if (bytes <= 64 * 1024 || tile <= 64) break;
         tile /= 2;
     }
+    // the smallest tile and the bank together miss the LDS (ComplexF64 decimation by 63 with 5000 taps: 144 + 40 KiB): the taps stay in L2
+    if (a.pfb_in_lds && span * (int64_t)sizeof(A) + pfb_bytes > 150 * 1024) a.pfb_in_lds = 0;
     const int64_t lds_bytes = span * (int64_t)sizeof(A) + (a.pfb_in_lds ? pfb_bytes : 0);
     if (lds_bytes > 150 * 1024) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "filter too long for the polyphase kernel (tapsPerPhase=%lld)", (long long)f->tp);
     a.tile = tile;
@@ -1581,7 +1583,10 @@ bool fir_fast_ok(const mdsp_fir_s* f, int P) {
     if (f->acc_double || f->x_dtype != MDSP_F32 || f->tp > 64) return false;
     if (MDSP_DBG(fir_generic) || tunables().fir_exact || f->exact) return false;
     if (P >= 2 && (f->M > f->L || f->L < P)) return false;
-    return cdiv(f->L, P) <= 256;
+    if (cdiv(f->L, P) > 256) return false;
+    // the smallest tile fir_fast_launch stages is RL = 256 / NP rounds of M samples: a long decimation (1//200: 205 KiB) does not fit the LDS
+    const int64_t RL = std::max<int64_t>(1, 256 / cdiv(f->L, (int64_t)P));
+    return (RL * f->M + f->M + (f->tp + 7) / 8 * 8 + P) * (int64_t)sizeof(float) <= 150 * 1024;
 }
 
 template <int P> int fir_fast_dispatch(mdsp_fir_s* f, const FirArgs& a, hipStream_t st) {

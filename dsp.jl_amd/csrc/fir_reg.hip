@@ -182,12 +182,18 @@ template <typename XS, typename A, typename R, int P> int dispatch_tpc(FirRegArg
     }
     MDSP_FAIL(MDSP_ERR_ASSERTION, "no register-tap instantiation for %d taps per phase", a.tp);
 }
+// the largest tile launch() stages: Q = RL rounds (more only while the ~48 KiB budget holds) of M samples plus the window, within the 150 KiB of LDS
+// (a long decimation, Float64 1//1000: 256 rounds of 1000 samples, would not fit)
+bool lds_fits(int tpc, int P, int abytes, int64_t L, int64_t M) {
+    const int64_t NP = cdiv(L, (int64_t)P), RL = NP <= 256 ? std::max<int64_t>(1, 256 / NP) : 1;
+    return (RL * M + M + tpc + P - 1) * abytes <= 150 * 1024;
+}
 int choose_p(int x_dtype, bool acc_double, int64_t tp, int64_t L, int64_t M) {
-    const int tpc = tpc_of(tp), rbytes = acc_double ? 8 : 4;
+    const int tpc = tpc_of(tp), rbytes = acc_double ? 8 : 4, abytes = rbytes * (dtype_is_complex(x_dtype) ? 2 : 1);
     if (tpc == 0 || L > 1024) return 0;
-    (void)x_dtype;
-    if (M <= L && L >= 2 && fits(tpc, 2, rbytes, cdiv(L, 2)) && !(rbytes == 8 && tpc > 48) && tpc <= 64) return 2;
-    if (fits(tpc, 1, rbytes, L)) return 1;
+    // P = 2 has only the 256-thread instantiation (launch): more than 256 phase groups take P = 1, whose 1024-thread form covers L <= 1024
+    if (M <= L && L >= 2 && cdiv(L, 2) <= 256 && fits(tpc, 2, rbytes, cdiv(L, 2)) && !(rbytes == 8 && tpc > 48) && tpc <= 64 && lds_fits(tpc, 2, abytes, L, M)) return 2;
+    if (fits(tpc, 1, rbytes, L) && lds_fits(tpc, 1, abytes, L, M)) return 1;
     return 0;
 }
 template <typename XS, typename A, typename R> int dispatch_p(int P, FirRegArgs& a, int64_t nch, hipStream_t st) {
