@@ -20,7 +20,7 @@ from .filters import (FIRFilter, fftfilt, fftfilt_, tdfilt, tdfilt_, resample, i
 from .multitaper import (MTConfig, MTSpectrogramConfig, MTCrossSpectraConfig, MTCoherenceConfig, CrossPowerSpectra, Coherence,  # noqa: F401
                          coherence, dpss_config, mt_pgram, mt_pgram_, mt_spectrogram, mt_spectrogram_, mt_cross_power_spectra,
                          mt_cross_power_spectra_, mt_coherence, mt_coherence_)
-from .periodograms import (Periodogram, Spectrogram, WelchConfig, arraysplit, fftshift, periodogram, welch_pgram, welch_pgram_,  # noqa: F401
+from .periodograms import (Periodogram, Periodogram2, Spectrogram, WelchConfig, arraysplit, fftshift, periodogram, welch_pgram, welch_pgram_,  # noqa: F401
                            spectrogram, stft, power, freq, time, frame_count)
 from .comm import Comm  # noqa: F401
 from .channels import (channel_shard, welch_channel_mean, frame_shard, frame_span, welch_time_split,  # noqa: F401

@@ -108,6 +108,11 @@ PROTOTYPES = {
     "mdsp_stft_exec": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
     "mdsp_stft_exec_host": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, ci]),
     "mdsp_hilbert": (ci, [vp, i64, i64, i64, ci, vp, i64, vp]),
+    "mdsp_periodogram2_plan_create": (ci, [pvp, i64, i64, i64, i64, cd, ci, ci, ci]),
+    "mdsp_periodogram2_plan_destroy": (ci, [vp]),
+    "mdsp_periodogram2_plan_info": (ci, [vp, pi64, pi64, pint]),
+    "mdsp_periodogram2_exec": (ci, [vp, vp, i64, vp, i64, vp]),
+    "mdsp_periodogram2_geometry_for": (ci, [i64, i64, pi64, pi64, pi64]),
     "mdsp_tdfir_state_exec": (ci, [vp, i64, ci, vp, i64, i64, i64, vp, i64, vp, vp]),
     "mdsp_extrapolate": (ci, [vp, i64, i64, i64, ci, i64, vp, i64, vp]),
     "mdsp_mt_plan_create": (ci, [pvp, i64, i64, vp, i64, vp, ci, ci, ci]),

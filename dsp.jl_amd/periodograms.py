@@ -24,6 +24,14 @@ class Periodogram:
 
 
 @dataclass
+class Periodogram2:
+    """periodograms.jl:284-288: the 2-D periodogram, power (nfft1, nfft2) with the frequencies of each axis."""
+    power: object
+    freq1: np.ndarray
+    freq2: np.ndarray
+
+
+@dataclass
 class Spectrogram:
     """periodograms.jl:773-777."""
     power: object
@@ -37,8 +45,8 @@ def power(p):
 
 
 def freq(p):
-    """periodograms.jl:329."""
-    return p.freq
+    """periodograms.jl:329-330 (a ``Periodogram2`` gives the tuple ``(freq1, freq2)``)."""
+    return (p.freq1, p.freq2) if isinstance(p, Periodogram2) else p.freq
 
 
 def time(p):
@@ -53,11 +61,18 @@ def _is_twosided_freq(f: np.ndarray) -> bool:
 
 
 def fftshift(p):
-    """``fftshift(p::Periodogram)`` / ``fftshift(p::Spectrogram)`` (periodograms.jl:331-333, :778-780): centre the zero
-    frequency of a two-sided estimate; one-sided (and already shifted) ones are returned as they are."""
+    """``fftshift(p::Periodogram)`` / ``fftshift(p::Spectrogram)`` / ``fftshift(p::Periodogram2)`` (periodograms.jl:331-339, :778-780):
+    centre the zero frequency of a two-sided estimate; one-sided (and already shifted) ones are returned as they are."""
+    xp = _dev.torch if _dev.is_device_array(p.power) else np
+    if isinstance(p, Periodogram2):      # both axes when freq1 is two-sided, else only the second (:334-339)
+        two1, two2 = _is_twosided_freq(p.freq1), _is_twosided_freq(p.freq2)
+        if two1:
+            return Periodogram2(xp.fft.fftshift(p.power), np.fft.fftshift(p.freq1), np.fft.fftshift(p.freq2) if two2 else p.freq2)
+        if two2:
+            return Periodogram2(xp.fft.fftshift(p.power, 1), p.freq1, np.fft.fftshift(p.freq2))
+        return p
     if not _is_twosided_freq(p.freq):
         return p
-    xp = _dev.torch if _dev.is_device_array(p.power) else np
     power = xp.fft.fftshift(p.power, 0)        # frequency is the first axis of both layouts
     f = np.fft.fftshift(p.freq)
     return Spectrogram(power, f, p.time) if isinstance(p, Spectrogram) else Periodogram(power, f)
@@ -197,10 +212,23 @@ def spectrogram(s, n: int | None = None, noverlap: int | None = None, *, oneside
     return Spectrogram(out, util.rfftfreq(nfft, fs) if onesided else util.fftfreq(nfft, fs), t)
 
 
-def periodogram(s, *, onesided: bool | None = None, nfft: int | None = None, fs=1, window=None,
-                engine: int = _lib.ENGINE_AUTO) -> Periodogram:
-    """``periodogram(s; onesided, nfft, fs, window)`` (periodograms.jl:393-417): the single-segment PSD."""
+_UNSET = object()   # keyword not given (DSP.jl's methods differ in which keywords they take)
+
+
+def periodogram(s, *, onesided=_UNSET, nfft=None, fs=1, window=_UNSET, radialsum=_UNSET, radialavg=_UNSET,
+                engine: int = _lib.ENGINE_AUTO):
+    """``periodogram(s; onesided, nfft, fs, window)`` (periodograms.jl:393-417): the single-segment PSD of a vector, and of a
+    complex matrix column by column; ``periodogram(s::AbstractMatrix{<:Real}; nfft, fs, radialsum, radialavg)`` (:473-509): the 2-D
+    periodogram of a real matrix (``Periodogram2``, or a radial ``Periodogram``)."""
     sdt = _dev.np_dtype_of(s)
+    if len(s.shape) == 2 and sdt.kind != "c":
+        if onesided is not _UNSET or window is not _UNSET:
+            raise TypeError("periodogram(s::AbstractMatrix{<:Real}; nfft, fs, radialsum, radialavg) takes no onesided / window")
+        return _periodogram2(s, sdt, nfft, fs, radialsum is not _UNSET and bool(radialsum), radialavg is not _UNSET and bool(radialavg), engine)
+    if radialsum is not _UNSET or radialavg is not _UNSET:
+        raise TypeError("radialsum / radialavg are keywords of the 2-D periodogram of a real matrix only")
+    onesided = None if onesided is _UNSET else onesided
+    window = None if window is _UNSET else window
     cplx = sdt.kind == "c"
     length = int(s.shape[0])
     onesided = (not cplx) if onesided is None else bool(onesided)
@@ -211,6 +239,63 @@ def periodogram(s, *, onesided: bool | None = None, nfft: int | None = None, fs=
         raise DomainError(f"nfft must be >= n = length(s) (nfft={nfft}, n={length})")  # :397
     out = stft(s, length, 0, True, onesided=onesided, nfft=nfft, fs=fs, window=window, engine=engine)
     return Periodogram(out[:, 0], util.rfftfreq(nfft, fs) if onesided else util.fftfreq(nfft, fs))
+
+
+class _P2Plan:
+    def __init__(self, n1, n2, nfft1, nfft2, fs, ptype, dtype, engine):
+        self._h = C.c_void_p()
+        _lib.check(_lib.lib().mdsp_periodogram2_plan_create(C.byref(self._h), n1, n2, nfft1, nfft2, float(fs), ptype, _dev.md_dtype(dtype), engine))
+        no, ws, eng = C.c_int64(), C.c_int64(), C.c_int()
+        _lib.check(_lib.lib().mdsp_periodogram2_plan_info(self._h, C.byref(no), C.byref(ws), C.byref(eng)))
+        self.nout, self.workspace_bytes, self.engine = no.value, ws.value, eng.value
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().mdsp_periodogram2_plan_destroy(self._h)
+        except Exception:
+            pass
+
+
+def _periodogram2(s, sdt, nfft, fs, radialsum, radialavg, engine):
+    """periodograms.jl:473-509 on the device (mdsp_periodogram2_*)."""
+    n1, n2 = (int(k) for k in s.shape)
+    if nfft is None:
+        nfft = util.nextfastfft((n1, n2))                                              # nextfastfft(size(s))
+    if not (isinstance(nfft, (tuple, list)) and len(nfft) == 2 and all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in nfft)):
+        raise TypeError(f"nfft of the 2-D periodogram is an NTuple{{2,Int}}, got {nfft!r}")
+    N1, N2 = (int(k) for k in nfft)
+    if not (n1 <= N1 and n2 <= N2):
+        raise ArgumentError("nfft must be >= size(s)")                                  # :477
+    if not (n1 > 1 and n2 > 1):
+        raise ArgumentError("dimensions of s must be > 1")                              # :478
+    if radialsum and radialavg:
+        raise ArgumentError("radialsum and radialavg are mutually exclusive")           # :480
+    ptype = 1 if radialsum else 2 if radialavg else 0
+    S = util.fftintype(sdt)
+    T = util.fftabs2type(S)
+    plan = _plancache.plans.get(("periodogram2", _plancache.ctx_key(), n1, n2, N1, N2, float(fs), ptype, np.dtype(S).str, engine),
+                                lambda: _P2Plan(n1, n2, N1, N2, fs, ptype, S, engine))
+    cols, _ = _dev.to_columns(s, S)            # (n2, n1): column j of s contiguous, like the Julia matrix
+    if ptype == 0:
+        out = _dev.empty_columns(N2, N1, T)
+        _lib.check(_lib.lib().mdsp_periodogram2_exec(plan._h, _dev.ptr(cols), n1, _dev.ptr(out), N1, _dev.stream_ptr()))
+        res = out.t()                          # (N1, N2), first axis contiguous
+        if not _dev.is_device_array(s):
+            res = res.cpu().numpy()
+        return Periodogram2(res, util.fftfreq(N1, fs), util.fftfreq(N2, fs))
+    out = _dev.torch.empty(plan.nout, dtype=_dev.torch_dtype(T), device=cols.device)
+    _lib.check(_lib.lib().mdsp_periodogram2_exec(plan._h, _dev.ptr(cols), n1, _dev.ptr(out), plan.nout, _dev.stream_ptr()))
+    return Periodogram(out if _dev.is_device_array(s) else out.cpu().numpy(), np.arange(plan.nout) * (fs / min(N1, N2)))
+
+
+def periodogram2_geometry(nfft1: int, nfft2: int):
+    """(kmax, wc, partials) of the radial reduction for nfft = (nfft1, nfft2): host arithmetic of the library, no device needed."""
+    kmax, parts = C.c_int64(), C.c_int64()
+    _lib.check(_lib.lib().mdsp_periodogram2_geometry_for(int(nfft1), int(nfft2), C.byref(kmax), None, C.byref(parts)))
+    wc = np.zeros(kmax.value, dtype=np.int64)
+    _lib.check(_lib.lib().mdsp_periodogram2_geometry_for(int(nfft1), int(nfft2), C.byref(kmax), wc.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(parts)))
+    return kmax.value, wc, parts.value
 
 
 _MISSING = object()

@@ -260,6 +260,31 @@ int mdsp_stft_exec_host(mdsp_stft_plan plan, const void* s_host, int64_t len, in
                         int64_t ldo, int64_t chs, int flags);
 
 /* ------------------------------------------------------------------------------------------------------
+ * 2-D periodogram (periodograms.jl:473-509, kernels fft2pow2! / fft2pow2radial! :175-232)
+ *   periodogram(s::AbstractMatrix{<:Real}; nfft = (nfft1, nfft2), fs, radialsum, radialavg) of a real (n1, n2) matrix:
+ *   ptype 0  out (nfft1, nfft2) = abs2.(fft(s zero-padded to nfft)) / (fs n1 n2)     (norm2 = length(s), :488)
+ *   ptype 1  radialsum: out (kmax) with kmax = min(nfft1, nfft2) / 2 + 1, the wave-number bins of :191-225
+ *   ptype 2  radialavg: the same divided by the wave counts wc
+ *   Output element type fftabs2type: Float32 for Float32 input, else Float64.  dtype: MDSP_F32 / MDSP_F64 (fftintype applied by the
+ *   caller).  engine goes to the plan's two internal STFT plans (rows, then columns); engine_used reports the engine both took, or
+ *   MDSP_ENGINE_AUTO when they took different ones.  Checks, before any device work, in the reference's order: nfft >= size(s)
+ *   (MDSP_ERR_ARGUMENT "nfft must be >= size(s)"), n1 > 1 && n2 > 1, ptype in 0..2, dtype real.  fs must be positive (the internal
+ *   column plan's normalisation).  The radial reduction uses no atomics: one plan gives bit-identical results exec after exec.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct mdsp_periodogram2_plan_s* mdsp_periodogram2_plan;
+int mdsp_periodogram2_plan_create(mdsp_periodogram2_plan* plan, int64_t n1, int64_t n2, int64_t nfft1, int64_t nfft2,
+                                  double fs, int ptype, int dtype, int engine);
+int mdsp_periodogram2_plan_destroy(mdsp_periodogram2_plan plan);
+int mdsp_periodogram2_plan_info(mdsp_periodogram2_plan plan, int64_t* nout /* nfft1*nfft2 or kmax */,
+                                int64_t* workspace_bytes, int* engine_used);
+/* s_dev: (n1, n2), column stride lds >= n1.  out_dev: (nfft1, nfft2), column stride ldo >= nfft1 (ptype 0; rows nfft1 .. ldo-1 are not
+ * written), or kmax values (ptype 1 / 2; ldo unused). */
+int mdsp_periodogram2_exec(mdsp_periodogram2_plan plan, const void* s_dev, int64_t lds, void* out_dev, int64_t ldo, void* stream);
+/* Pure host arithmetic, no device needed (like mdsp_ols_geometry_for): kmax, the wave counts wc (kmax values, may be NULL) and the
+ * number of Float64 row partials of the radial reduction (the sum over rows of each row's bin range).  nfft1, nfft2 >= 2. */
+int mdsp_periodogram2_geometry_for(int64_t nfft1, int64_t nfft2, int64_t* kmax, int64_t* wc_host, int64_t* partials);
+
+/* ------------------------------------------------------------------------------------------------------
  * Multitaper spectral estimation (src/multitaper.jl)
  *   plan    = MTConfig (:5-135): frames of n samples, nfft, `ntapers` tapers (n x ntapers, column-major Float64,
  *             e.g. dpss(n, nw, ntapers)), inverse normalisations r[taper] (fs ./ taper_weights, :127-131)

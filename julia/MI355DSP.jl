@@ -20,7 +20,7 @@ module MI355DSP
 using LinearAlgebra: SymTridiagonal, eigen
 
 export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, tdfilt!, conv, conv!, xcorr, hilbert,
-       Periodogram, Spectrogram, power, freq, arraysplit, periodogram, WelchConfig, welch_pgram, welch_pgram!,
+       Periodogram, Periodogram2, Spectrogram, power, freq, fftshift, arraysplit, periodogram, WelchConfig, welch_pgram, welch_pgram!,
        spectrogram, stft, FIRFilter, resample, resample_filter, reset!, setphase!, timedelay, inputlength, outputlength,
        DF2TFilter, filtfilt, nextfastfft, optimalfftfiltlength, Comm, welch_channel_mean, welch_reset!, welch_accumulate!,
        welch_finalize, welch_allreduce!, pin!, unpin!, MTConfig, mt_pgram, mt_pgram!, MTSpectrogramConfig, mt_spectrogram,
@@ -680,6 +680,56 @@ function periodogram(s::AbstractVector{T}; onesided::Bool=T <: Real, nfft::Int=n
     nfft >= length(s) || throw(DomainError((; nfft, n=length(s)), "nfft must be >= n = length(s)"))        # :397
     p = stft(s, length(s), 0, true; onesided, nfft, fs, window)
     Periodogram(vec(p), onesided ? rfftfreq(nfft, fs) : fftfreq(nfft, fs))
+end
+
+# 2-D periodogram   periodograms.jl:284-288 (Periodogram2), :330-339 (freq, fftshift), :473-509 (periodogram of a real matrix)
+struct Periodogram2{T,F1<:AbstractVector,F2<:AbstractVector,M<:AbstractMatrix{T}} <: TFR{T}
+    power::M
+    freq1::F1
+    freq2::F2
+end
+freq(p::Periodogram2) = (p.freq1, p.freq2)
+# the reference's three methods: both dimensions shift when freq1 is two-sided (fftfreq), only dimension 2 when freq1 is not
+twosided(f::AbstractVector) = length(f) > 1 && any(<(0), diff(f))
+shifted(f::AbstractVector) = circshift(f, length(f) >> 1)
+function fftshift(p::Periodogram2)
+    twosided(p.freq1) && return Periodogram2(circshift(p.power, size(p.power) .>> 1), shifted(p.freq1), twosided(p.freq2) ? shifted(p.freq2) : p.freq2)
+    twosided(p.freq2) && return Periodogram2(circshift(p.power, (0, size(p.power, 2) >> 1)), p.freq1, shifted(p.freq2))
+    p
+end
+# kmax, the wave counts and the number of radial row partials for nfft (host arithmetic, no device)
+function periodogram2_geometry(nfft::NTuple{2,Int})
+    kmax, parts = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_periodogram2_geometry_for, lib), Cint, (Int64, Int64, Ref{Int64}, Ptr{Int64}, Ref{Int64}), nfft[1], nfft[2], kmax, C_NULL, parts))
+    wc = zeros(Int64, kmax[])
+    check(ccall((:mdsp_periodogram2_geometry_for, lib), Cint, (Int64, Int64, Ref{Int64}, Ptr{Int64}, Ref{Int64}), nfft[1], nfft[2], kmax, wc, parts))
+    (Int(kmax[]), wc, Int(parts[]))
+end
+function periodogram(s::Union{AbstractMatrix{T},DeviceArray{T,2}}; nfft::NTuple{2,Int}=nextfastfft.(size(s)), fs::Real=1,
+                     radialsum::Bool=false, radialavg::Bool=false, engine=ENGINE_AUTO) where {T<:Real}
+    n1, n2 = size(s)
+    n1 <= nfft[1] && n2 <= nfft[2] || throw(ArgumentError("nfft must be >= size(s)"))                     # :477
+    n1 > 1 && n2 > 1 || throw(ArgumentError("dimensions of s must be > 1"))                               # :478
+    radialsum && radialavg && throw(ArgumentError("radialsum and radialavg are mutually exclusive"))      # :480
+    ptype = radialsum ? 1 : radialavg ? 2 : 0
+    S = fftintype(T)
+    O = fftabs2type(S)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_periodogram2_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Int64, Cdouble, Cint, Cint, Cint),
+                h, n1, n2, nfft[1], nfft[2], fs, ptype, mdtype(S), engine))
+    try
+        nout, ws, eng = Ref{Int64}(0), Ref{Int64}(0), Ref{Cint}(0)
+        check(ccall((:mdsp_periodogram2_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Cint}), h[], nout, ws, eng))
+        sd = todevice(s, S)
+        out = ptype == 0 ? DeviceArray{O}(nfft) : DeviceArray{O}((Int(nout[]),))
+        check(ccall((:mdsp_periodogram2_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+                    h[], sd.ptr, n1, out.ptr, nfft[1], C_NULL))
+        power = download(out)          # the result types hold host arrays (as welch_pgram's Periodogram)
+        ptype == 0 && return Periodogram2(power, fftfreq(nfft[1], fs), fftfreq(nfft[2], fs))
+        Periodogram(power, (0:Int(nout[]) - 1) .* (fs / minimum(nfft)))
+    finally
+        ccall((:mdsp_periodogram2_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
 end
 
 # ---------------------------------------------------------------------------------------------- filter design needed as INPUTS of the path
