@@ -107,6 +107,7 @@ PROTOTYPES = {
     "mdsp_stft_plan_info": (ci, [vp, pi64, pint]),
     "mdsp_stft_exec": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
     "mdsp_stft_exec_host": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, ci]),
+    "mdsp_spectral_route_for": (ci, [ci, ci, i64, ci, pint, pint, pint]),
     "mdsp_hilbert": (ci, [vp, i64, i64, i64, ci, vp, i64, vp]),
     "mdsp_periodogram2_plan_create": (ci, [pvp, i64, i64, i64, i64, cd, ci, ci, ci]),
     "mdsp_periodogram2_plan_destroy": (ci, [vp]),

@@ -206,6 +206,15 @@ int get(const std::string& key, void** out, const std::function<int(void**)>& ma
 
 size_t real_size(int dtype) { return dtype_is_double(dtype) ? 8 : 4; }
 
+// Welch / STFT plans: the RESOLVED engine, kernel family and split (mdsp_spectral_route_for) are part of the key, so that a plan created under other
+// tunables (mdsp_reload_tunables, mdsp_set_knob) is not handed out for a route it did not prepare -- as the OLS key holds the resolved geometry.  Where
+// the arguments have no route, plan creation reports the error and nothing is cached.
+void put_route(std::string& k, int kind, int dtype, int64_t nfft, int engine) {
+    int eng = engine, route = -1, r0 = 0;
+    (void)mdsp_spectral_route_for(kind, dtype, nfft, engine, &eng, &route, &r0);
+    put(k, eng); put(k, route); put(k, r0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -238,7 +247,8 @@ int mdsp_welch_plan_cached(mdsp_welch_plan* plan, int64_t n, int64_t noverlap, i
     *plan = nullptr;
     if (n < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "negative size");
     std::string k = base_key('w', stream);
-    put(k, n); put(k, noverlap); put(k, nfft); put(k, r); put(k, onesided); put(k, dtype); put(k, engine == MDSP_ENGINE_AUTO ? tunables().engine : engine);
+    put(k, n); put(k, noverlap); put(k, nfft); put(k, r); put(k, onesided); put(k, dtype);
+    put_route(k, 0, dtype, nfft, engine);
     put(k, (char)(window_host != nullptr));
     if (window_host) put(k, window_host, (size_t)n * sizeof(double));
     void* h = nullptr;
@@ -255,7 +265,7 @@ int mdsp_stft_plan_cached(mdsp_stft_plan* plan, int64_t n, int64_t noverlap, int
     if (n < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "negative size");
     std::string k = base_key('s', stream);
     put(k, n); put(k, noverlap); put(k, nfft); put(k, r); put(k, onesided); put(k, psd_only); put(k, dtype);
-    put(k, engine == MDSP_ENGINE_AUTO ? tunables().engine : engine);
+    put_route(k, 1, dtype, nfft, engine);
     put(k, (char)(window_host != nullptr));
     if (window_host) put(k, window_host, (size_t)n * sizeof(double));
     void* h = nullptr;

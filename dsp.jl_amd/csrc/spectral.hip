@@ -22,6 +22,7 @@
 #include <atomic>
 #include <cstdlib>
 
+#include <map>
 #include <memory>
 #include <mutex>
 #include <vector>
@@ -681,8 +682,16 @@ bool fused_size_ok(int dtype, int64_t nfft) {
     }
 }
 
+struct SpecRoute {
+    int engine = MDSP_ENGINE_ROCFFT, route = MDSP_ROUTE_ROCFFT, r0 = 0;
+};
+
+// The kernel family (MDSP_ROUTE_*) and engine of a Welch (kind 0: sums of |X|^2) or STFT / spectrogram / periodogram / multitaper (kind 1: columns)
+// plan: decided here, once, when the plan is created, from the tunables of that moment -- the plan records it and its exec dispatches on the record.
+// The only reader of the knobs that steer the choice (MDSP_GX, MDSP_BIGFFT, MDSP_ENGINE, MDSP_GEN_CT_F64_MAX) apart from the predicates it calls.
+//
 // round 6: the run-time-schedule kernel (spectral_gx.h) takes every 7-smooth size it plans that has neither a register-resident power-of-two kernel
-// nor a compile-time schedule -- in front of the round-2 LDS kernel, the multi-pass engine and the rocFFT pipeline.  kind: 0 Welch sums, 1 columns.
+// nor a compile-time schedule -- in front of the round-2 LDS kernel, the multi-pass engine and the rocFFT pipeline.
 // Measured against both (profiles/r06_gx_vs_r5.json: Float32 / Float64 / ComplexF32 / ComplexF64, 1125 .. 65536 points):
 //   Welch          : 2 - 7 x either at every size but the powers of two from 32768 (the multi-pass engine's two register stages: a tie)
 //   real columns   : 1.1 - 6 x, a tie with rocFFT at R0 >= 5 (12500, 40000); 16384 = 2 x 8192 loses 8 % to the multi-pass engine
@@ -692,68 +701,74 @@ bool fused_size_ok(int dtype, int64_t nfft) {
 // on the fused column step, 100000 = 8 x 12500 0.66 / 0.49, 131072 0.74 / 0.54; a tie at R0 = 5 (81920: 0.69 / 0.69); the fused step wins below (65536 = 4 x 16384
 // 0.74 / 0.81, 32768 0.76 / 1.01).  Beyond eight rows there is no fused step: 150000 .. 500000 points 0.50 - 0.67 against the multi-pass engine's 0.08 - 0.18, 2^19 =
 // 32 x 16384 0.73 against 0.52 on the engine's rows form.  MDSP_GX=8: wherever a split exists (A/B), MDSP_GX=-1: never.
-int ctrows_r0(int dtype, int64_t nfft) {
+int choose_spectral_route(int engine, int dtype, int64_t nfft, int kind, SpecRoute* out) {
     const int m = tunables().gx;
-    if (m == 0 || m == -1 || m == 4 || m == 5 || m == 6 || ctbig_ok(dtype, nfft) || (m == 3 && dtype_is_double(dtype))) return 0;
-    const int any = ctrows_split(dtype, nfft, 2);
-    if (any == 0) return 0;
-    if (m == 8) return any;
-    const int fused = ctcols_split(dtype, nfft);
-    return (fused == 0 || fused >= (dtype_is_double(dtype) ? 5 : 6)) ? any : 0;   // (Float64, r06s71 / r06s72: 48000 = 5 x 9600 0.60 against 0.51 fused, 57600 0.62 / 0.45; a tie at R0 = 4)
-}
-bool use_gx(int dtype, int64_t nfft, bool direct, int kind) {
-    const int m = tunables().gx;
-    if (m == 0) return false;
-    if (kind == 0 && m != 4 && m != 5 && ctbig_preferred(dtype, nfft)) return true;
-    if (kind == 0 && m != 4 && !fused_size_ok(dtype, nfft) && !gen_ct_size(dtype, nfft, direct) && ((m != 5 && ctbig_ok(dtype, nfft)) || ctcols_split(dtype, nfft) > 0 || ctrows_r0(dtype, nfft) > 0))
-        return true;   // Welch sums on a compile-time schedule (one workgroup, or R0 x S rows): whatever the run-time-schedule kernel plans
-    if (kind == 1 && m != 4 && m != 5 && !fused_size_ok(dtype, nfft) && !gen_ct_size(dtype, nfft, direct) && ctbig_cols_ok(dtype, nfft))
-        return true;   // columns on a single-workgroup compile-time schedule (spectral_ctbig_cols.hip), 16384 points included
-    if (!gx_size_ok(dtype, nfft)) return false;
-    if (m >= 2) return true;
+    const bool dbl = dtype_is_double(dtype), cplx = dtype_is_complex(dtype);
+    const bool direct = kind == 0 || cplx;   // the last pass is consumed from registers (spectral_gen.h)
     const bool pow2 = (nfft & (nfft - 1)) == 0;
-    if (pow2 && nfft >= (kind == 0 ? 32768 : 16384) && big::size_ok(dtype, nfft) && !(kind == 0 && ctcols_split(dtype, nfft) > 0)) return false;   // (Welch, Float32: 4 x / 8 x 8192 on the compile-time rows)
-    return !fused_size_ok(dtype, nfft) && !gen_ct_size(dtype, nfft, direct);
-}
-// ... and where AUTO prefers it to the rocFFT pipeline (engine = FUSED takes it wherever use_gx says so)
-bool gx_wins(int dtype, int64_t nfft, int kind) {
-    if (kind == 0 || !dtype_is_complex(dtype)) return true;
-    if (tunables().gx != 4 && tunables().gx != 5 && ctbig_cols_ok(dtype, nfft)) return true;   // single-workgroup compile-time columns: 1.6 - 2.9 TB/s against rocFFT's 0.3 - 1.4 (r06s58)
-    if (nfft <= 4096) return false;
-    return gx_split_r0(dtype, nfft) <= 4;
-}
-// the multi-pass engine takes what no single-workgroup kernel does
-bool use_big(int dtype, int64_t nfft, bool direct, int kind) {
-    return !use_gx(dtype, nfft, direct, kind) && !fused_size_ok(dtype, nfft) && !gen_size_ok(dtype, nfft) && !gen_ct_size(dtype, nfft, direct) && big::size_ok(dtype, nfft);
-}
-
-// kind: 0 = Welch (sums of |X|^2), 1 = STFT / spectrogram / periodogram columns
-int resolve_engine(int engine, int dtype, int64_t nfft, int* out, int kind = 1) {
-    int eng = engine;
-    if (eng == MDSP_ENGINE_AUTO) eng = tunables().engine;
-    // fused: the register-resident power-of-two sizes, and the mixed-radix LDS kernel for the other 7-smooth sizes nextfastfft returns
-    const bool direct = kind == 0 || dtype_is_complex(dtype);   // the last pass is consumed from registers (spectral_gen.h)
-    const bool big_ok = use_big(dtype, nfft, direct, kind);   // round 5: the multi-pass engine (bigfft.hip) for everything above the one-workgroup sizes
-    const bool gx_ok = use_gx(dtype, nfft, direct, kind);
-    const bool fused_ok = gx_ok || fused_size_ok(dtype, nfft) || gen_size_ok(dtype, nfft) || gen_ct_size(dtype, nfft, direct) || big_ok;
-    // AUTO takes the mixed-radix kernel where it measured faster than the rocFFT pipeline (profiles/r02g_mixed.json, 2^27 samples): Welch and
-    // real-signal columns up to 4096 points (1.4-3x), complex columns above (1.6x); elsewhere the two are within 20 % and rocFFT is kept.
-    // Round 3: the sizes with a compile-time schedule (spectral_gen.h, Float32 / ComplexF32) beat the rocFFT pipeline 2-9x in every mode
-    // (profiles/r03d_mixed_ct.json) and are always taken.
-    // ... taken by AUTO where it measured faster than the rocFFT pipeline (profiles/r05_big_vs_rocfft.json, 2^26 samples): powers of two from 16384 on
-    // (two-stage register passes: Welch 1.5 - 2.2x, columns 1.1 - 1.4x; the 8192-point Float64 split loses 0.7 - 0.8x), other 7-smooth sizes from
-    // 50000 points on for Welch and real-signal columns (1.1 - 1.7x at 50000 / 100000 / 125000 / 200000; complex columns lose 0.7 - 0.9x there, and
-    // below 50000 the generic passes' small tiles lose to rocFFT at most sizes: 8400 .. 10000 0.7x, 20000 0.5x, 40000 1.0x)
-    const bool pow2 = (nfft & (nfft - 1)) == 0;
-    const bool big_wins = big_ok && (pow2 ? nfft >= 16384 : (nfft >= 50000 && !(kind == 1 && dtype_is_complex(dtype))));
-    const bool gen_wins = (gx_ok && gx_wins(dtype, nfft, kind)) || big_wins || fused_size_ok(dtype, nfft) || gen_ct_size(dtype, nfft, direct) ||
-                          (gen_size_ok(dtype, nfft) && ((nfft <= 4096) == (kind == 0 || !dtype_is_complex(dtype))));
-    if (eng == MDSP_ENGINE_AUTO) eng = gen_wins ? MDSP_ENGINE_FUSED : MDSP_ENGINE_ROCFFT;
-    if (eng == MDSP_ENGINE_FUSED && !fused_ok)
+    const bool reg = fused_size_ok(dtype, nfft), gen = !reg && gen_size_ok(dtype, nfft), ct = gen_ct_size(dtype, nfft, direct);
+    const bool ctbig = !(m == 3 && dbl) && ctbig_ok(dtype, nfft);            // (MDSP_GX=3: Float64 stays on the run-time schedule, A/B)
+    const bool ctbig_cols = !(m == 3 && dbl) && ctbig_cols_ok(dtype, nfft);
+    const int cols = kind == 0 ? ctcols_split(dtype, nfft) : 0;
+    const int rows = [&] {
+        if (kind != 0 || reg || m == 0 || m == -1 || m == 4 || m == 5 || m == 6 || ctbig || (m == 3 && dbl)) return 0;   // (rows above 4096 / 8192 points)
+        const int any = ctrows_split(dtype, nfft, 2);
+        if (any == 0 || m == 8) return any;
+        return (cols == 0 || cols >= (dbl ? 5 : 6)) ? any : 0;   // (Float64, r06s71 / r06s72: 48000 = 5 x 9600 0.60 against 0.51 fused, 57600 0.62 / 0.45; a tie at R0 = 4)
+    }();
+    const bool gx = [&] {   // a single-workgroup kernel of spectral_gx.h / spectral_ct*.hip
+        if (m == 0) return false;
+        if (kind == 0 && m != 4 && m != 5 && ctbig_preferred(dtype, nfft)) return true;
+        if (kind == 0 && m != 4 && !reg && !ct && ((m != 5 && ctbig) || cols > 0 || rows > 0))
+            return true;   // Welch sums on a compile-time schedule (one workgroup, or R0 x S rows): whatever the run-time-schedule kernel plans
+        if (kind == 1 && m != 4 && m != 5 && !reg && !ct && ctbig_cols)
+            return true;   // columns on a single-workgroup compile-time schedule (spectral_ctbig_cols.hip), 16384 points included
+        if (!gx_size_ok(dtype, nfft)) return false;
+        if (m >= 2) return true;
+        if (pow2 && nfft >= (kind == 0 ? 32768 : 16384) && big::size_ok(dtype, nfft) && cols == 0) return false;   // (Welch, Float32: 4 x / 8 x 8192 on the compile-time rows)
+        return !reg && !ct;
+    }();
+    const bool big = !gx && !reg && !gen && !ct && big::size_ok(dtype, nfft);   // round 5: the multi-pass engine (bigfft.hip) takes what no single-workgroup kernel does
+    int eng = engine == MDSP_ENGINE_AUTO ? tunables().engine : engine;
+    if (eng == MDSP_ENGINE_AUTO) {
+        // AUTO takes the mixed-radix kernel where it measured faster than the rocFFT pipeline (profiles/r02g_mixed.json, 2^27 samples): Welch and
+        // real-signal columns up to 4096 points (1.4-3x), complex columns above (1.6x); elsewhere the two are within 20 % and rocFFT is kept.
+        // Round 3: the sizes with a compile-time schedule (spectral_gen.h, Float32 / ComplexF32) beat the rocFFT pipeline 2-9x in every mode
+        // (profiles/r03d_mixed_ct.json) and are always taken.
+        // ... the multi-pass engine where it measured faster than the rocFFT pipeline (profiles/r05_big_vs_rocfft.json, 2^26 samples): powers of two from 16384 on
+        // (two-stage register passes: Welch 1.5 - 2.2x, columns 1.1 - 1.4x; the 8192-point Float64 split loses 0.7 - 0.8x), other 7-smooth sizes from
+        // 50000 points on for Welch and real-signal columns (1.1 - 1.7x at 50000 / 100000 / 125000 / 200000; complex columns lose 0.7 - 0.9x there, and
+        // below 50000 the generic passes' small tiles lose to rocFFT at most sizes: 8400 .. 10000 0.7x, 20000 0.5x, 40000 1.0x)
+        // ... and the run-time-schedule kernel everywhere but complex columns, which rocFFT serves faster below 4097 points and from R0 = 5 on --
+        // except on a single-workgroup compile-time schedule: 1.6 - 2.9 TB/s against rocFFT's 0.3 - 1.4 (r06s58)
+        const auto gx_wins = [&] { return kind == 0 || !cplx || (m != 4 && m != 5 && ctbig_cols) || (nfft > 4096 && gx_split_r0(dtype, nfft) <= 4); };
+        const bool big_wins = big && (pow2 ? nfft >= 16384 : (nfft >= 50000 && !(kind == 1 && cplx)));
+        const bool fused_wins = (gx && gx_wins()) || big_wins || reg || ct || (gen && ((nfft <= 4096) == (kind == 0 || !cplx)));
+        eng = fused_wins ? MDSP_ENGINE_FUSED : MDSP_ENGINE_ROCFFT;
+    }
+    if (eng == MDSP_ENGINE_FUSED && !(gx || reg || gen || ct || big))
         MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "fused engine supports nfft = 2^a 3^b 5^c 7^d (up to %d, or splitting into 2..4 factors of at most 512); got %lld",
-                  dtype_is_double(dtype) ? 4096 : 8192, (long long)nfft);
+                  dbl ? 4096 : 8192, (long long)nfft);
     if (eng != MDSP_ENGINE_FUSED && eng != MDSP_ENGINE_ROCFFT) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid engine %d", engine);
-    *out = eng;
+    SpecRoute r;
+    r.engine = eng;
+    if (eng == MDSP_ENGINE_ROCFFT) r.route = MDSP_ROUTE_ROCFFT;
+    else if (!gx) r.route = big ? MDSP_ROUTE_BIG : reg ? MDSP_ROUTE_POW2 : MDSP_ROUTE_GEN;
+    else if (kind == 1) r.route = (m != 4 && m != 5 && ctbig_cols) ? MDSP_ROUTE_CTBIG_COLS : MDSP_ROUTE_GX;
+    // R0 x a row size with a COMPILE-TIME schedule (16384 = 2 x 8192, 12500 = 5 x 2500, 20000 = 4 x 5000 ...): the same decomposition on the kernels of
+    // spectral_gen.h (spectral_ctcols.hip) -- about half the vector instructions per point of the run-time schedule
+    else if (m != 4 && m != 5 && ctbig) r.route = MDSP_ROUTE_CTBIG;   // one workgroup, compile-time schedule (spectral_ctbig.hip): 8400 .. 12500 points
+    else if (rows > 0) {
+        r.route = MDSP_ROUTE_CTROWS;
+        r.r0 = rows;
+    } else if (m != 4 && cols > 0) {   // rows of 8193 .. 16384 points first (MDSP_GX=6: without them), then Float64 rows of 4097 .. 9600 points
+        const int64_t S = nfft / cols;
+        r.r0 = cols;
+        if (m != 6 && ctcols_big_row_ok(dtype, S)) r.route = MDSP_ROUTE_CTCOLS_BIG;
+        else if (dbl && m != 6 && m != 3 && ctcols64_row_ok(S)) r.route = MDSP_ROUTE_CTCOLS_F64;
+        else r.route = MDSP_ROUTE_CTCOLS;
+    } else r.route = MDSP_ROUTE_GX;
+    *out = r;
     return MDSP_OK;
 }
 
@@ -779,6 +794,12 @@ template <typename R> int upload_roots(DevBuf& buf, int64_t n) {
     MDSP_TRY(buf.reserve(sizeof(cx<R>) * (size_t)n));
     MDSP_HIP(hipMemcpy(buf.p, w.data(), sizeof(cx<R>) * (size_t)n, hipMemcpyHostToDevice));
     return MDSP_OK;
+}
+
+// the plan's table of nfft roots, for the routes whose kernels read it (the others build their own, much shorter, tables)
+int upload_plan_roots(DevBuf& table, int route, int dtype, int64_t nfft) {
+    if (route != MDSP_ROUTE_POW2 && route != MDSP_ROUTE_GEN) return MDSP_OK;
+    return dtype_is_double(dtype) ? upload_roots<double>(table, nfft) : upload_roots<float>(table, nfft);
 }
 
 int check_split(int64_t n, int64_t noverlap, int64_t nfft) {
@@ -1582,6 +1603,14 @@ int welch_run_variant(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int* n
     return MDSP_OK;
 }
 
+// the accumulator now holds the fused engine's sums: Float64, nfft bins per channel (pair-packed full spectrum for real signals)
+void set_fused_sums(mdsp_welch_plan_s* pl) {
+    pl->acc_fresh = false;
+    pl->acc_nslices = 1;
+    pl->acc_nacc = (int)pl->nfft;
+    pl->acc_mode = dtype_is_complex(pl->dtype) ? 1 : (pl->onesided ? 3 : 4);
+}
+
 template <typename R, int N, bool CPLX>
 int welch_launch_n(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st) {
     using Gm = Geo<R, N>;
@@ -1699,119 +1728,89 @@ finalize:
     MDSP_TRY(reduce_partials(pl, pl->partial.as<double>(), pl->reduced.as<double>(), nslices, a.nch, N, pl->acc_fresh ? 0 : 1, st));
 reduced_done:
     if (rc != MDSP_OK) return rc;
-    pl->acc_fresh = false;
-    pl->acc_nslices = 1;
-    pl->acc_nacc = N;
-    pl->acc_mode = CPLX ? 1 : (pl->onesided ? 3 : 4);
+    set_fused_sums(pl);
     return MDSP_OK;
 }
 
 template <typename R, bool CPLX>
 int welch_accumulate_fused(mdsp_welch_plan_s* pl, const void* s, int64_t len, int64_t nch, int64_t lds_, hipStream_t st) {
-    const int64_t K = mdsp_frame_count(len, pl->n, pl->noverlap);
+    const int64_t K = mdsp_frame_count(len, pl->n, pl->noverlap), hop = pl->n - pl->noverlap, N = pl->nfft;
+    const double* win = pl->have_win ? pl->win.as<double>() : nullptr;
+    if (pl->route != MDSP_ROUTE_POW2 || K == 0) MDSP_TRY(pl->reduced.reserve(sizeof(double) * (size_t)nch * (size_t)N));
     if (K == 0) {
         if (pl->acc_fresh) {   // nothing to add; make the accumulator exist (zeros) so that a later finalize / all-reduce is defined
-            MDSP_TRY(pl->reduced.reserve(sizeof(double) * (size_t)nch * (size_t)pl->nfft));
-            MDSP_HIP(hipMemsetAsync(pl->reduced.p, 0, sizeof(double) * (size_t)nch * (size_t)pl->nfft, st));
-            pl->acc_fresh = false;
-            pl->acc_nslices = 1;
-            pl->acc_nacc = (int)pl->nfft;
-            pl->acc_mode = CPLX ? 1 : (pl->onesided ? 3 : 4);
+            MDSP_HIP(hipMemsetAsync(pl->reduced.p, 0, sizeof(double) * (size_t)nch * (size_t)N, st));
+            set_fused_sums(pl);
         }
         return MDSP_OK;
     }
-    if (use_gx(pl->dtype, pl->nfft, true, 0)) {   // run-time-schedule kernel (spectral_gx.h): partial rows per group of workgroups, same Float64 accumulator protocol
-        GxArgs g{};
-        g.s = s; g.lds_ = lds_; g.K = K; g.hop = pl->n - pl->noverlap; g.nch = nch;
-        g.n = (int)pl->n; g.nfft = (int)pl->nfft; g.nout = (int)pl->nout; g.onesided = pl->onesided; g.r = pl->r;
-        int64_t ngroups = 0;
-        // R0 x a row size with a COMPILE-TIME schedule (16384 = 2 x 8192, 12500 = 5 x 2500, 20000 = 4 x 5000 ...): the same decomposition on the kernels of
-        // spectral_gen.h (spectral_ctcols.hip) -- about half the vector instructions per point of the run-time schedule
-        if (tunables().gx != 4 && tunables().gx != 5 && ctbig_ok(pl->dtype, pl->nfft))   // one workgroup, compile-time schedule (spectral_ctbig.hip): 8400 .. 12500 points
-            MDSP_TRY(ctbig_welch(pl->ctcols, pl->dtype, s, lds_, K, pl->n - pl->noverlap, nch, (int)pl->n, pl->nfft, pl->have_win ? pl->win.as<double>() : nullptr, st, &ngroups,
-                                 &pl->partial));
-        else if (const int r0rows = ctrows_r0(pl->dtype, pl->nfft); r0rows > 0) {   // nfft = R0 x S in two kernels (spectral_ctrows.hip): straight into the accumulator
-            MDSP_TRY(pl->reduced.reserve(sizeof(double) * (size_t)nch * (size_t)pl->nfft));
-            MDSP_TRY(ctrows_welch(pl->ctrows, pl->dtype, r0rows, s, lds_, K, pl->n - pl->noverlap, nch, (int)pl->n, pl->nfft, pl->have_win ? pl->win.as<double>() : nullptr,
-                                  pl->reduced.as<double>(), pl->acc_fresh, st));
-            pl->acc_fresh = false;
-            pl->acc_nslices = 1;
-            pl->acc_nacc = (int)pl->nfft;
-            pl->acc_mode = CPLX ? 1 : (pl->onesided ? 3 : 4);
+    // the single-workgroup kernels leave partial rows per group of workgroups in pl->partial (same Float64 accumulator protocol), reduced below
+    int64_t ngroups = 0;
+    switch (pl->route) {
+        case MDSP_ROUTE_POW2: {
+            SpecArgs a{};
+            a.s = s; a.table = pl->table.p; a.win = win; a.len = len; a.lds_ = lds_; a.K = K; a.hop = hop; a.units_per_ch = CPLX ? K : cdiv(K, 2); a.nch = nch;
+            a.n = (int)pl->n; a.nout = (int)pl->nout; a.onesided = pl->onesided; a.r = pl->r;
+            switch (N) {
+                case 256: return welch_launch_n<R, 256, CPLX>(pl, a, st);
+                case 512: return welch_launch_n<R, 512, CPLX>(pl, a, st);
+                case 1024: return welch_launch_n<R, 1024, CPLX>(pl, a, st);
+                case 2048: return welch_launch_n<R, 2048, CPLX>(pl, a, st);
+                case 4096: return welch_launch_n<R, 4096, CPLX>(pl, a, st);
+                case 8192:
+                    if constexpr (sizeof(R) == 4) return welch_launch_n<R, 8192, CPLX>(pl, a, st);
+                default: break;
+            }
+            MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "fused Welch does not support nfft=%lld", (long long)N);
+        }
+        case MDSP_ROUTE_GEN: {   // mixed-radix sizes: everything through LDS (spectral_gen.h)
+            GenArgs g{};
+            g.s = s; g.roots = pl->table.p; g.win = win;
+            g.len = len; g.lds_ = lds_; g.K = K; g.hop = hop; g.nch = nch; g.units_per_ch = CPLX ? K : cdiv(K, 2);
+            g.n = (int)pl->n; g.N = (int)N; g.nout = (int)pl->nout; g.onesided = pl->onesided; g.r = pl->r;
+            if (lean_window_needed(N, sizeof(R) == 8)) {
+                if (!pl->winr_ready) MDSP_TRY(lean_window<R>(pl->winr, win, g.n, N, st));
+                pl->winr_ready = true;
+                g.winr = pl->winr.p;
+            }
+            MDSP_TRY((gen_launch<R, CPLX, 0>(g, nch, st, &ngroups, &pl->partial)));
+            break;
+        }
+        case MDSP_ROUTE_GX: {   // run-time-schedule kernel (spectral_gx.h)
+            GxArgs g{};
+            g.s = s; g.lds_ = lds_; g.K = K; g.hop = hop; g.nch = nch;
+            g.n = (int)pl->n; g.nfft = (int)N; g.nout = (int)pl->nout; g.onesided = pl->onesided; g.r = pl->r;
+            MDSP_TRY((gx_launch<R, CPLX, 0>(pl->gx, g, win, pl->dtype, st, &ngroups, &pl->partial)));
+            break;
+        }
+        case MDSP_ROUTE_CTBIG:   // one workgroup, compile-time schedule (spectral_ctbig.hip): 8400 .. 12500 points
+            MDSP_TRY(ctbig_welch(pl->ctcols, pl->dtype, s, lds_, K, hop, nch, (int)pl->n, N, win, st, &ngroups, &pl->partial));
+            break;
+        case MDSP_ROUTE_CTCOLS_BIG:   // R0 x a row size with a compile-time schedule (spectral_ctcols*.hip)
+            MDSP_TRY(ctcols_big_welch(pl->ctcols, pl->dtype, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, win, st, &ngroups, &pl->partial));
+            break;
+        case MDSP_ROUTE_CTCOLS_F64:
+            MDSP_TRY(ctcols64_welch(pl->ctcols, CPLX, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, win, st, &ngroups, &pl->partial));
+            break;
+        case MDSP_ROUTE_CTCOLS:
+            MDSP_TRY(ctcols_welch(pl->ctcols, pl->dtype, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, win, st, &ngroups, &pl->partial));
+            break;
+        case MDSP_ROUTE_CTROWS:   // nfft = R0 x S in two kernels (spectral_ctrows.hip): straight into the accumulator
+            MDSP_TRY(ctrows_welch(pl->ctrows, pl->dtype, pl->r0, s, lds_, K, hop, nch, (int)pl->n, N, win, pl->reduced.as<double>(), pl->acc_fresh, st));
+            set_fused_sums(pl);
             return MDSP_OK;
-        } else if (tunables().gx != 4 && ctcols_split(pl->dtype, pl->nfft) > 0)
-            MDSP_TRY(ctcols_welch(pl->ctcols, pl->dtype, s, lds_, K, pl->n - pl->noverlap, nch, (int)pl->n, pl->nfft, pl->have_win ? pl->win.as<double>() : nullptr, st, &ngroups,
-                                  &pl->partial));
-        else
-        MDSP_TRY((gx_launch<R, CPLX, 0>(pl->gx, g, pl->have_win ? pl->win.as<double>() : nullptr, pl->dtype, st, &ngroups, &pl->partial)));
-        const int N = (int)pl->nfft;
-        MDSP_TRY(pl->reduced.reserve(sizeof(double) * (size_t)nch * (size_t)N));
-        MDSP_TRY(reduce_partials(pl, pl->partial.as<double>(), pl->reduced.as<double>(), (int)ngroups, nch, N, pl->acc_fresh ? 0 : 1, st));
-        pl->acc_fresh = false;
-        pl->acc_nslices = 1;
-        pl->acc_nacc = N;
-        pl->acc_mode = CPLX ? 1 : (pl->onesided ? 3 : 4);
-        return MDSP_OK;
-    }
-    if (use_big(pl->dtype, pl->nfft, true, 0)) {   // nfft above the one-workgroup sizes: channel by channel through the multi-pass engine, same accumulator protocol
-        using TT = std::conditional_t<CPLX, cx<R>, R>;
-        const int64_t N = pl->nfft;
-        MDSP_TRY(pl->reduced.reserve(sizeof(double) * (size_t)nch * (size_t)N));
-        for (int64_t c = 0; c < nch; ++c)
-            MDSP_TRY(big::welch(pl->big, pl->dtype, pl->n, N, static_cast<const TT*>(s) + c * lds_, K, pl->n - pl->noverlap,
-                                pl->have_win ? pl->win.as<double>() : nullptr, pl->reduced.as<double>() + c * N, pl->acc_fresh, st));
-        pl->acc_fresh = false;
-        pl->acc_nslices = 1;
-        pl->acc_nacc = (int)N;
-        pl->acc_mode = CPLX ? 1 : (pl->onesided ? 3 : 4);
-        return MDSP_OK;
-    }
-    SpecArgs a{};
-    a.s = s;
-    a.table = pl->table.p;
-    a.win = pl->have_win ? pl->win.as<double>() : nullptr;
-    a.len = len;
-    a.lds_ = lds_;
-    a.K = K;
-    a.hop = pl->n - pl->noverlap;
-    a.units_per_ch = CPLX ? K : cdiv(K, 2);
-    a.nch = nch;
-    a.n = (int)pl->n;
-    a.nout = (int)pl->nout;
-    a.onesided = pl->onesided;
-    a.r = pl->r;
-    if (!fused_size_ok(pl->dtype, pl->nfft)) {   // mixed-radix sizes: everything through LDS (spectral_gen.h), same Float64 accumulator protocol
-        GenArgs g{};
-        g.s = s; g.roots = pl->table.p; g.win = a.win;
-        g.len = len; g.lds_ = lds_; g.K = K; g.hop = a.hop; g.nch = nch; g.units_per_ch = a.units_per_ch;
-        g.n = a.n; g.N = (int)pl->nfft; g.nout = a.nout; g.onesided = a.onesided; g.r = a.r;
-        if (lean_window_needed(pl->nfft, sizeof(R) == 8)) {
-            if (!pl->winr_ready) MDSP_TRY(lean_window<R>(pl->winr, a.win, a.n, pl->nfft, st));
-            pl->winr_ready = true;
-            g.winr = pl->winr.p;
+        case MDSP_ROUTE_BIG: {   // nfft above the one-workgroup sizes: channel by channel through the multi-pass engine, straight into the accumulator
+            using TT = std::conditional_t<CPLX, cx<R>, R>;
+            for (int64_t c = 0; c < nch; ++c)
+                MDSP_TRY(big::welch(pl->big, pl->dtype, pl->n, N, static_cast<const TT*>(s) + c * lds_, K, hop, win, pl->reduced.as<double>() + c * N, pl->acc_fresh, st));
+            set_fused_sums(pl);
+            return MDSP_OK;
         }
-        int64_t nslots = 0;
-        MDSP_TRY((gen_launch<R, CPLX, 0>(g, nch, st, &nslots, &pl->partial)));
-        const int N = (int)pl->nfft;
-        MDSP_TRY(pl->reduced.reserve(sizeof(double) * (size_t)nch * (size_t)N));
-        MDSP_TRY(reduce_partials(pl, pl->partial.as<double>(), pl->reduced.as<double>(), (int)nslots, nch, N, pl->acc_fresh ? 0 : 1, st));
-        pl->acc_fresh = false;
-        pl->acc_nslices = 1;
-        pl->acc_nacc = N;
-        pl->acc_mode = CPLX ? 1 : (pl->onesided ? 3 : 4);
-        return MDSP_OK;
+        default: MDSP_FAIL(MDSP_ERR_ASSERTION, "Welch plan with route %d on the fused engine", pl->route);
     }
-    switch (pl->nfft) {
-        case 256: return welch_launch_n<R, 256, CPLX>(pl, a, st);
-        case 512: return welch_launch_n<R, 512, CPLX>(pl, a, st);
-        case 1024: return welch_launch_n<R, 1024, CPLX>(pl, a, st);
-        case 2048: return welch_launch_n<R, 2048, CPLX>(pl, a, st);
-        case 4096: return welch_launch_n<R, 4096, CPLX>(pl, a, st);
-        case 8192:
-            if constexpr (sizeof(R) == 4) return welch_launch_n<R, 8192, CPLX>(pl, a, st);
-        default: break;
-    }
-    MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "fused Welch does not support nfft=%lld", (long long)pl->nfft);
+    MDSP_TRY(reduce_partials(pl, pl->partial.as<double>(), pl->reduced.as<double>(), (int)ngroups, nch, (int)N, pl->acc_fresh ? 0 : 1, st));
+    set_fused_sums(pl);
+    return MDSP_OK;
 }
 
 }  // namespace
@@ -1830,6 +1829,7 @@ int gx_run(int id, const GxArgs& a, unsigned grid_x, unsigned grid_y, int thread
 // (the rows of K transforms of nch x S points, column pass done) -> pl->reduced[row][bin] (+)= |FFT_S(frame)|^2 on the single-workgroup kernels.
 // pl: a complex, two-sided, window-free FUSED plan of S points (n = nfft = S).
 int welch_rows_accumulate(mdsp_welch_plan_s* pl, const void* work, int64_t K, int64_t hop, int64_t nch, hipStream_t st) {
+    if (pl->route != MDSP_ROUTE_POW2) MDSP_FAIL(MDSP_ERR_ASSERTION, "rows of %lld points on route %d, not the power-of-two kernel", (long long)pl->nfft, pl->route);
     if (K <= 0 || nch <= 0) return MDSP_OK;
     SpecArgs a{};
     a.s = work;
@@ -1853,6 +1853,17 @@ int welch_rows_accumulate(mdsp_welch_plan_s* pl, const void* work, int64_t K, in
 
 extern "C" {
 
+int mdsp_spectral_route_for(int kind, int dtype, int64_t nfft, int engine, int* engine_used, int* route, int* r0) {
+    if (!dtype_valid(dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid dtype %d", dtype);
+    if (kind != 0 && kind != 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid kind %d (0: Welch sums, 1: STFT columns)", kind);
+    SpecRoute r;
+    MDSP_TRY(choose_spectral_route(engine, dtype, nfft, kind, &r));
+    if (engine_used) *engine_used = r.engine;
+    if (route) *route = r.route;
+    if (r0) *r0 = r.r0;
+    return MDSP_OK;
+}
+
 int mdsp_welch_plan_create(mdsp_welch_plan* plan, int64_t n, int64_t noverlap, int64_t nfft, const double* window_host, double r, int onesided,
                            int dtype, int engine) {
     if (!plan) MDSP_FAIL(MDSP_ERR_ARGUMENT, "plan is NULL");
@@ -1862,11 +1873,13 @@ int mdsp_welch_plan_create(mdsp_welch_plan* plan, int64_t n, int64_t noverlap, i
     if (!(nfft >= n)) MDSP_FAIL(MDSP_ERR_DOMAIN, "nfft must be >= n (nfft=%lld, n=%lld)", (long long)nfft, (long long)n);
     MDSP_TRY(check_split(n, noverlap, nfft));
     if (!(r > 0)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "normalisation r must be positive");
-    int eng;
-    MDSP_TRY(resolve_engine(engine, dtype, nfft, &eng, 0));
+    SpecRoute rt;
+    MDSP_TRY(choose_spectral_route(engine, dtype, nfft, 0, &rt));
     auto pl = new mdsp_welch_plan_s();
     pl->dtype = dtype;
-    pl->engine = eng;
+    pl->engine = rt.engine;
+    pl->route = rt.route;
+    pl->r0 = rt.r0;
     pl->onesided = onesided ? 1 : 0;
     pl->n = n;
     pl->noverlap = noverlap;
@@ -1881,8 +1894,7 @@ int mdsp_welch_plan_create(mdsp_welch_plan* plan, int64_t n, int64_t noverlap, i
         if (st == MDSP_OK && hipMemcpy(pl->win.p, window_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
             st = set_error(MDSP_ERR_DEVICE, "window upload failed");
     }
-    if (st == MDSP_OK && eng == MDSP_ENGINE_FUSED && !use_big(dtype, nfft, true, 0) && !use_gx(dtype, nfft, true, 0))   // (the multi-pass engine and the run-time-schedule kernel build their own, much shorter, tables)
-        st = dtype_is_double(dtype) ? upload_roots<double>(pl->table, nfft) : upload_roots<float>(pl->table, nfft);
+    if (st == MDSP_OK) st = upload_plan_roots(pl->table, pl->route, dtype, nfft);
     if (st != MDSP_OK) {
         delete pl;
         return st;
@@ -2022,6 +2034,7 @@ extern "C" int mdsp_channel_sum(const void* psd_dev, int64_t nout, int64_t nch, 
 // ======================================================================================================
 struct mdsp_stft_plan_s {
     int dtype = MDSP_F32, engine = MDSP_ENGINE_ROCFFT, onesided = 1, psd_only = 0;
+    int route = MDSP_ROUTE_ROCFFT, r0 = 0;   // the kernel family exec runs, decided at creation (choose_spectral_route)
     int64_t n = 0, noverlap = 0, nfft = 0, nout = 0;
     double r = 1;
     bool have_win = false;
@@ -2167,73 +2180,78 @@ template <typename R, int N, bool CPLX> int stft_launch_n(mdsp_stft_plan_s* pl, 
 
 template <typename R, bool CPLX>
 int stft_exec_fused(mdsp_stft_plan_s* pl, const void* s, int64_t len, int64_t nch, int64_t lds_, void* out, int64_t ldo, int64_t chs, hipStream_t st) {
-    const int64_t K = mdsp_frame_count(len, pl->n, pl->noverlap);
+    const int64_t K = mdsp_frame_count(len, pl->n, pl->noverlap), hop = pl->n - pl->noverlap;
     if (K == 0) return MDSP_OK;
-    if (use_gx(pl->dtype, pl->nfft, CPLX, 1)) {   // run-time-schedule kernel (spectral_gx.h); multitaper plans come here once per taper (accumulate)
-        if (tunables().gx != 4 && tunables().gx != 5 && ctbig_cols_ok(pl->dtype, pl->nfft)) {   // ... or a single-workgroup compile-time schedule (spectral_ctbig_cols.hip)
+    const double* win = pl->have_win ? pl->win_ptr : nullptr;
+    // multitaper plans come here once per taper (accumulate) on every route but the power-of-two kernels of real signals
+    switch (pl->route) {
+        case MDSP_ROUTE_POW2: {
+            SpecArgs a{};
+            a.s = s; a.out = out; a.table = pl->table.p; a.win = win; a.accumulate = pl->accumulate; a.ntapers = pl->mt_ntapers; a.rinv = pl->mt_rinv;
+            a.len = len; a.lds_ = lds_; a.K = K; a.hop = hop; a.units_per_ch = K; a.nch = nch; a.ldo = ldo; a.chs = chs;
+            a.n = (int)pl->n; a.nout = (int)pl->nout; a.onesided = pl->onesided; a.r = pl->r;
+            switch (pl->nfft) {
+                case 256: return stft_launch_n<R, 256, CPLX>(pl, a, st);
+                case 512: return stft_launch_n<R, 512, CPLX>(pl, a, st);
+                case 1024: return stft_launch_n<R, 1024, CPLX>(pl, a, st);
+                case 2048: return stft_launch_n<R, 2048, CPLX>(pl, a, st);
+                case 4096: return stft_launch_n<R, 4096, CPLX>(pl, a, st);
+                case 8192:
+                    if constexpr (sizeof(R) == 4) return stft_launch_n<R, 8192, CPLX>(pl, a, st);
+                default: break;
+            }
+            MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "fused STFT does not support nfft=%lld", (long long)pl->nfft);
+        }
+        case MDSP_ROUTE_GEN: {   // mixed-radix sizes (spectral_gen.h)
+            GenArgs g{};
+            g.s = s; g.out = out; g.roots = pl->table.p; g.win = win;
+            g.len = len; g.lds_ = lds_; g.K = K; g.hop = hop; g.nch = nch; g.ldo = ldo; g.chs = chs;
+            g.units_per_ch = CPLX ? K : cdiv(K, 2);
+            g.n = (int)pl->n; g.N = (int)pl->nfft; g.nout = (int)pl->nout; g.onesided = pl->onesided; g.psd = pl->psd_only; g.accumulate = pl->accumulate; g.r = pl->r;
+            if (CPLX && lean_window_needed(pl->nfft, sizeof(R) == 8)) {   // (per launch: the window pointer of a multitaper plan changes between tapers)
+                MDSP_TRY(lean_window<R>(pl->winr, win, g.n, pl->nfft, st));
+                g.winr = pl->winr.p;
+            }
+            int64_t nslots = 0;
+            return gen_launch<R, CPLX, 1>(g, nch, st, &nslots, nullptr);
+        }
+        case MDSP_ROUTE_GX: {   // run-time-schedule kernel (spectral_gx.h)
+            GxArgs g{};
+            g.s = s; g.out = out; g.lds_ = lds_; g.K = K; g.hop = hop; g.nch = nch; g.ldo = ldo; g.chs = chs;
+            g.n = (int)pl->n; g.nfft = (int)pl->nfft; g.nout = (int)pl->nout; g.onesided = pl->onesided; g.psd = pl->psd_only; g.accumulate = pl->accumulate; g.r = pl->r;
+            int64_t ngroups = 0;
+            return gx_launch<R, CPLX, 1>(pl->gx, g, win, pl->dtype, st, &ngroups, nullptr);
+        }
+        case MDSP_ROUTE_CTBIG_COLS: {   // a single-workgroup compile-time schedule (spectral_ctbig_cols.hip)
             CtBigColsArgs c{};
-            c.s = s; c.out = out; c.win = pl->have_win ? pl->win_ptr : nullptr; c.len = len; c.lds_ = lds_; c.K = K; c.hop = pl->n - pl->noverlap; c.nch = nch; c.ldo = ldo; c.chs = chs;
+            c.s = s; c.out = out; c.win = win; c.len = len; c.lds_ = lds_; c.K = K; c.hop = hop; c.nch = nch; c.ldo = ldo; c.chs = chs;
             c.n = (int)pl->n; c.nfft = pl->nfft; c.nout = (int)pl->nout; c.onesided = pl->onesided; c.psd = pl->psd_only; c.accumulate = pl->accumulate; c.r = pl->r;
             return ctbig_stft(pl->ctbig, pl->dtype, c, st);
         }
-        GxArgs g{};
-        g.s = s; g.out = out; g.lds_ = lds_; g.K = K; g.hop = pl->n - pl->noverlap; g.nch = nch; g.ldo = ldo; g.chs = chs;
-        g.n = (int)pl->n; g.nfft = (int)pl->nfft; g.nout = (int)pl->nout; g.onesided = pl->onesided; g.psd = pl->psd_only; g.accumulate = pl->accumulate; g.r = pl->r;
-        int64_t ngroups = 0;
-        return gx_launch<R, CPLX, 1>(pl->gx, g, pl->have_win ? pl->win_ptr : nullptr, pl->dtype, st, &ngroups, nullptr);
-    }
-    if (use_big(pl->dtype, pl->nfft, CPLX, 1)) {   // nfft above the one-workgroup sizes (bigfft.hip); multitaper plans come here once per taper (accumulate)
-        using TT = std::conditional_t<CPLX, cx<R>, R>;
-        const size_t osz = pl->psd_only ? sizeof(R) : sizeof(cx<R>);
-        for (int64_t c = 0; c < nch; ++c)
-            MDSP_TRY(big::stft(pl->big, pl->dtype, pl->n, pl->nfft, static_cast<const TT*>(s) + c * lds_, K, pl->n - pl->noverlap, pl->have_win ? pl->win_ptr : nullptr,
-                               static_cast<char*>(out) + (size_t)(c * chs) * osz, ldo, pl->nout, pl->onesided, pl->psd_only, pl->accumulate, pl->r, st));
-        return MDSP_OK;
-    }
-    SpecArgs a{};
-    a.s = s;
-    a.out = out;
-    a.table = pl->table.p;
-    a.win = pl->have_win ? pl->win_ptr : nullptr;
-    a.accumulate = pl->accumulate;
-    a.ntapers = pl->mt_ntapers;
-    a.rinv = pl->mt_rinv;
-    a.len = len;
-    a.lds_ = lds_;
-    a.K = K;
-    a.hop = pl->n - pl->noverlap;
-    a.units_per_ch = K;
-    a.nch = nch;
-    a.ldo = ldo;
-    a.chs = chs;
-    a.n = (int)pl->n;
-    a.nout = (int)pl->nout;
-    a.onesided = pl->onesided;
-    a.r = pl->r;
-    if (!fused_size_ok(pl->dtype, pl->nfft)) {   // mixed-radix sizes (spectral_gen.h); multitaper plans come here once per taper (accumulate)
-        GenArgs g{};
-        g.s = s; g.out = out; g.roots = pl->table.p; g.win = a.win;
-        g.len = len; g.lds_ = lds_; g.K = K; g.hop = a.hop; g.nch = nch; g.ldo = ldo; g.chs = chs;
-        g.units_per_ch = CPLX ? K : cdiv(K, 2);
-        g.n = a.n; g.N = (int)pl->nfft; g.nout = a.nout; g.onesided = a.onesided; g.psd = pl->psd_only; g.accumulate = pl->accumulate; g.r = a.r;
-        if (CPLX && lean_window_needed(pl->nfft, sizeof(R) == 8)) {   // (per launch: the window pointer of a multitaper plan changes between tapers)
-            MDSP_TRY(lean_window<R>(pl->winr, a.win, a.n, pl->nfft, st));
-            g.winr = pl->winr.p;
+        case MDSP_ROUTE_BIG: {   // nfft above the one-workgroup sizes (bigfft.hip)
+            using TT = std::conditional_t<CPLX, cx<R>, R>;
+            const size_t osz = pl->psd_only ? sizeof(R) : sizeof(cx<R>);
+            for (int64_t c = 0; c < nch; ++c)
+                MDSP_TRY(big::stft(pl->big, pl->dtype, pl->n, pl->nfft, static_cast<const TT*>(s) + c * lds_, K, hop, win,
+                                   static_cast<char*>(out) + (size_t)(c * chs) * osz, ldo, pl->nout, pl->onesided, pl->psd_only, pl->accumulate, pl->r, st));
+            return MDSP_OK;
         }
-        int64_t nslots = 0;
-        return gen_launch<R, CPLX, 1>(g, nch, st, &nslots, nullptr);
+        default: MDSP_FAIL(MDSP_ERR_ASSERTION, "STFT plan with route %d on the fused engine", pl->route);
     }
-    switch (pl->nfft) {
-        case 256: return stft_launch_n<R, 256, CPLX>(pl, a, st);
-        case 512: return stft_launch_n<R, 512, CPLX>(pl, a, st);
-        case 1024: return stft_launch_n<R, 1024, CPLX>(pl, a, st);
-        case 2048: return stft_launch_n<R, 2048, CPLX>(pl, a, st);
-        case 4096: return stft_launch_n<R, 4096, CPLX>(pl, a, st);
-        case 8192:
-            if constexpr (sizeof(R) == 4) return stft_launch_n<R, 8192, CPLX>(pl, a, st);
-        default: break;
+}
+
+int stft_dispatch(mdsp_stft_plan_s* plan, const void* s_dev, int64_t len, int64_t nch, int64_t lds_, void* out_dev, int64_t ldo, int64_t chs, hipStream_t st) {
+    const bool cplx = dtype_is_complex(plan->dtype), dbl = dtype_is_double(plan->dtype);
+    if (plan->engine == MDSP_ENGINE_ROCFFT) {
+        if (cplx) return dbl ? stft_exec_rocfft<double, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
+                             : stft_exec_rocfft<float, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
+        return dbl ? stft_exec_rocfft<double, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
+                   : stft_exec_rocfft<float, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
     }
-    MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "fused STFT does not support nfft=%lld", (long long)pl->nfft);
+    if (cplx) return dbl ? stft_exec_fused<double, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
+                         : stft_exec_fused<float, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
+    return dbl ? stft_exec_fused<double, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
+               : stft_exec_fused<float, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
 }
 
 }  // namespace
@@ -2248,11 +2266,13 @@ int mdsp_stft_plan_create(mdsp_stft_plan* plan, int64_t n, int64_t noverlap, int
     if (onesided && dtype_is_complex(dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "cannot compute one-sided FFT of a complex signal");
     MDSP_TRY(check_split(n, noverlap, nfft));
     if (psd_only && !(r > 0)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "normalisation r must be positive");
-    int eng;
-    MDSP_TRY(resolve_engine(engine, dtype, nfft, &eng));
+    SpecRoute rt;
+    MDSP_TRY(choose_spectral_route(engine, dtype, nfft, 1, &rt));
     auto pl = new mdsp_stft_plan_s();
     pl->dtype = dtype;
-    pl->engine = eng;
+    pl->engine = rt.engine;
+    pl->route = rt.route;
+    pl->r0 = rt.r0;
     pl->onesided = onesided ? 1 : 0;
     pl->psd_only = psd_only ? 1 : 0;
     pl->n = n;
@@ -2268,8 +2288,7 @@ int mdsp_stft_plan_create(mdsp_stft_plan* plan, int64_t n, int64_t noverlap, int
             st = set_error(MDSP_ERR_DEVICE, "window upload failed");
         pl->win_ptr = pl->win.as<double>();
     }
-    if (st == MDSP_OK && eng == MDSP_ENGINE_FUSED && !use_big(dtype, nfft, dtype_is_complex(dtype), 1) && !use_gx(dtype, nfft, dtype_is_complex(dtype), 1))
-        st = dtype_is_double(dtype) ? upload_roots<double>(pl->table, nfft) : upload_roots<float>(pl->table, nfft);
+    if (st == MDSP_OK) st = upload_plan_roots(pl->table, pl->route, dtype, nfft);
     if (st != MDSP_OK) {
         delete pl;
         return st;
@@ -2300,18 +2319,7 @@ int mdsp_stft_exec(mdsp_stft_plan plan, const void* s_dev, int64_t len, int64_t 
     if (ldo < plan->nout) MDSP_FAIL(MDSP_ERR_DIMENSION, "column stride smaller than the column length");
     if (nch > 1 && (lds_ < len || chs < ldo * (K - 1) + plan->nout)) MDSP_FAIL(MDSP_ERR_DIMENSION, "channel stride too small");
     if (nch > 65535) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "more than 65535 channels per call");
-    hipStream_t st = as_stream(stream);
-    const bool cplx = dtype_is_complex(plan->dtype), dbl = dtype_is_double(plan->dtype);
-    if (plan->engine == MDSP_ENGINE_ROCFFT) {
-        if (cplx) return dbl ? stft_exec_rocfft<double, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
-                             : stft_exec_rocfft<float, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
-        return dbl ? stft_exec_rocfft<double, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
-                   : stft_exec_rocfft<float, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
-    }
-    if (cplx) return dbl ? stft_exec_fused<double, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
-                         : stft_exec_fused<float, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
-    return dbl ? stft_exec_fused<double, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
-               : stft_exec_fused<float, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
+    return stft_dispatch(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, as_stream(stream));
 }
 
 // stft / spectrogram of host arrays (periodograms.jl:872-897 takes a host vector and returns a host matrix): channel by channel, runs of whole
@@ -2433,19 +2441,6 @@ __global__ __launch_bounds__(256) void coherence_kernel(const cx<R>* __restrict_
     out[idx] = sqrt(v.x * v.x + v.y * v.y) / sqrt(d1.x * d2.x - d1.y * d2.y);
 }
 
-int stft_dispatch(mdsp_stft_plan_s* plan, const void* s_dev, int64_t len, int64_t nch, int64_t lds_, void* out_dev, int64_t ldo, int64_t chs, hipStream_t st) {
-    const bool cplx = dtype_is_complex(plan->dtype), dbl = dtype_is_double(plan->dtype);
-    if (plan->engine == MDSP_ENGINE_ROCFFT) {
-        if (cplx) return dbl ? stft_exec_rocfft<double, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
-                             : stft_exec_rocfft<float, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
-        return dbl ? stft_exec_rocfft<double, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
-                   : stft_exec_rocfft<float, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
-    }
-    if (cplx) return dbl ? stft_exec_fused<double, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
-                         : stft_exec_fused<float, true>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
-    return dbl ? stft_exec_fused<double, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st)
-               : stft_exec_fused<float, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
-}
 
 }  // namespace
 
@@ -2463,12 +2458,14 @@ int mdsp_mt_plan_create(mdsp_mt_plan* plan, int64_t n, int64_t nfft, const doubl
     if (!tapers_host || !r_host) MDSP_FAIL(MDSP_ERR_ARGUMENT, "tapers / r are NULL");
     for (int64_t k = 0; k < ntapers; ++k)
         if (!(r_host[k] > 0)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "normalisation r must be positive");
-    int eng;
-    MDSP_TRY(resolve_engine(engine, dtype, nfft, &eng));
+    SpecRoute rt;
+    MDSP_TRY(choose_spectral_route(engine, dtype, nfft, 1, &rt));
     std::unique_ptr<mdsp_mt_plan_s> pl(new mdsp_mt_plan_s());
     mdsp_stft_plan_s& st = pl->st;
     st.dtype = dtype;
-    st.engine = eng;
+    st.engine = rt.engine;
+    st.route = rt.route;
+    st.r0 = rt.r0;
     st.onesided = onesided ? 1 : 0;
     st.n = n;
     st.noverlap = 0;
@@ -2486,7 +2483,7 @@ int mdsp_mt_plan_create(mdsp_mt_plan* plan, int64_t n, int64_t nfft, const doubl
     for (int64_t k = 0; k < ntapers; ++k) w[(size_t)k] = 1.0 / r_host[k];
     MDSP_TRY(pl->rinv.reserve(sizeof(double) * (size_t)ntapers));
     MDSP_HIP(hipMemcpy(pl->rinv.p, w.data(), sizeof(double) * (size_t)ntapers, hipMemcpyHostToDevice));
-    if (eng == MDSP_ENGINE_FUSED) MDSP_TRY(dtype_is_double(dtype) ? upload_roots<double>(st.table, nfft) : upload_roots<float>(st.table, nfft));
+    MDSP_TRY(upload_plan_roots(st.table, st.route, dtype, nfft));
     *plan = pl.release();
     return MDSP_OK;
 }
@@ -2520,7 +2517,7 @@ int mdsp_mt_psd_exec(mdsp_mt_plan plan, const void* s_dev, int64_t len, int64_t 
     st.psd_only = 1;
     // real signals on the fused engine: every taper inside one launch (the frame pair stays in registers); otherwise one
     // pass per taper with the accumulate flag
-    if (st.engine == MDSP_ENGINE_FUSED && fused_size_ok(st.dtype, st.nfft) && !dtype_is_complex(st.dtype) && !MDSP_DBG(mt_passes) && !MDSP_DBG(stft_nopair)) {
+    if (st.route == MDSP_ROUTE_POW2 && !dtype_is_complex(st.dtype) && !MDSP_DBG(mt_passes) && !MDSP_DBG(stft_nopair)) {
         st.win_ptr = plan->wins.as<double>();
         st.r = plan->r[0];
         st.accumulate = 0;

@@ -54,7 +54,7 @@ template <typename R> int upload_roots_n(DevBuf& buf, int64_t n) {
 
 namespace mdsp {
 bool ctbig_ok(int dtype, int64_t nfft) {
-    if (dtype_is_double(dtype)) return tunables().gx != 3 && ctbig64_ok(nfft);   // (MDSP_GX=3: Float64 stays on the run-time schedule, A/B)
+    if (dtype_is_double(dtype)) return ctbig64_ok(nfft);
     switch (nfft) {
 #define MDSP_X(N, ...) case N:
         MDSP_CTBIG_SIZES(MDSP_X)
@@ -67,7 +67,7 @@ bool ctbig_ok(int dtype, int64_t nfft) {
     }
 }
 
-bool ctbig_preferred(int dtype, int64_t nfft) {   // ... in front of the all-mode schedule the size also has (spectral.hip use_gx)
+bool ctbig_preferred(int dtype, int64_t nfft) {   // ... in front of the all-mode schedule the size also has (spectral.hip choose_spectral_route)
     if (dtype_is_double(dtype)) return false;
     switch (nfft) {
 #define MDSP_X(N, ...) case N:

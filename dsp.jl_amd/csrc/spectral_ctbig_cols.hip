@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void cols_window_kernel(const double* __restri
 
 namespace mdsp {
 bool ctbig_cols_ok(int dtype, int64_t nfft) {
-    if (dtype_is_double(dtype)) return tunables().gx != 3 && ctbig64_ok(nfft);
+    if (dtype_is_double(dtype)) return ctbig64_ok(nfft);
     const bool cplx = dtype_is_complex(dtype);
     switch (nfft) {
 #define MDSP_X(N, ...) case N:

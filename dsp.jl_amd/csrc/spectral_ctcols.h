@@ -8,12 +8,13 @@ struct CtColsPlan {   // what a Welch plan keeps for it: roots of S and of nfft,
     bool ready = false;
     DevBuf roots, rootsN, win;
 };
-// the column factor R0 in 2 .. 8 with nfft / R0 among the instantiated row sizes (0: none)
+// the column factor R0 in 2 .. 8 with nfft / R0 among the instantiated row sizes (0: none); which of the three row forms below runs is decided with it
+// (spectral.hip choose_spectral_route)
 int ctcols_split(int dtype, int64_t nfft);
-// partial[(group, ch)][nfft] (+ reduce by the caller): Float64 sums of |Z|^2 per bin, natural order
-int ctcols_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, const double* win_dev,
-                 hipStream_t st, int64_t* ngroups, DevBuf* partial);
-// spectral_ctcols_big.hip: rows of 8193 .. 16384 points (the single-workgroup schedules of ctbig_sizes.h); ctcols_split / ctcols_welch route to them
+// partial[(group, ch)][nfft] (+ reduce by the caller): Float64 sums of |Z|^2 per bin, natural order -- rows on the mixed-radix compile-time schedules
+int ctcols_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0,
+                 const double* win_dev, hipStream_t st, int64_t* ngroups, DevBuf* partial);
+// spectral_ctcols_big.hip: rows of 8193 .. 16384 points (the single-workgroup schedules of ctbig_sizes.h)
 bool ctcols_big_row_ok(int dtype, int64_t S);
 int ctcols_big_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0,
                      const double* win_dev, hipStream_t st, int64_t* ngroups, DevBuf* partial);
@@ -21,7 +22,8 @@ int ctcols_big_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int
 bool ctcols64_row_ok(int64_t S);
 int ctcols64_welch(CtColsPlan& cp, bool cplx, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0, const double* win_dev,
                    hipStream_t st, int64_t* ngroups, DevBuf* partial);
-// spectral_ctbig.hip: nfft between 8193 and 16384 points with a single-workgroup compile-time schedule (Float32 / ComplexF32); cp holds the nfft roots
+// spectral_ctbig.hip: nfft between 8193 and 16384 points with a single-workgroup compile-time schedule (Float32 / ComplexF32); cp holds the nfft roots.
+// ctbig_ok / ctbig_cols_ok are the size tables alone (MDSP_GX=3 keeps Float64 off them in spectral.hip choose_spectral_route)
 bool ctbig_ok(int dtype, int64_t nfft);
 bool ctbig_preferred(int dtype, int64_t nfft);   // a size that also has an all-mode compile-time schedule, Welch sums faster here
 // (accumulate: the partial rows of an earlier launch with at least as many slots are added to instead of overwritten -- spectral_ctrows.hip)

@@ -103,14 +103,10 @@ int ctcols_split(int dtype, int64_t nfft) {
     return 0;
 }
 
-int ctcols_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, const double* win_dev,
-                 hipStream_t st, int64_t* ngroups, DevBuf* partial) {
-    const int R0 = ctcols_split(dtype, nfft);
-    if (R0 == 0) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld is not R0 x a compile-time row size", (long long)nfft);
+int ctcols_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0,
+                 const double* win_dev, hipStream_t st, int64_t* ngroups, DevBuf* partial) {
+    if (R0 < 2 || nfft % R0) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld is not %d x a compile-time row size", (long long)nfft, R0);
     const int64_t S = nfft / R0;
-    if (tunables().gx != 6 && ctcols_big_row_ok(dtype, S)) return ctcols_big_welch(cp, dtype, s, lds_, K, hop, nch, n, nfft, R0, win_dev, st, ngroups, partial);
-    if (dtype_is_double(dtype) && tunables().gx != 6 && tunables().gx != 3 && ctcols64_row_ok(S))
-        return ctcols64_welch(cp, dtype_is_complex(dtype), s, lds_, K, hop, nch, n, nfft, R0, win_dev, st, ngroups, partial);
     const bool dbl = dtype_is_double(dtype), cplx = dtype_is_complex(dtype);
     if (!cp.ready) {
         MDSP_TRY(dbl ? upload_roots_n<double>(cp.roots, S) : upload_roots_n<float>(cp.roots, S));

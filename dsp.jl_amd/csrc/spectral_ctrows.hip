@@ -6,7 +6,7 @@
 //             |Z|^2 into Float64 partial rows that persist over the chunks of a call;
 //   the sums leave in natural order: X[k1 + R0 k2] = FFT_S(row k1)[k2].
 // The work buffer is cut into chunks of MDSP_BIG_CHUNK_MIB (1 GiB; chunks of 128 MiB, to read the rows back from the Infinity Cache, measured 5 - 15 % SLOWER: more
-// launches, no cache effect -- r06s47).  Taken from R0 = 6 (spectral.hip ctrows_r0: the fused step wins to R0 = 4, a tie at 5).  (Also measured and dropped, r06s51: the row kernel of chunk c on a second stream beside the column kernel of chunk c + 1, six chunks on
+// launches, no cache effect -- r06s47).  Taken from R0 = 6 (spectral.hip choose_spectral_route: the fused step wins to R0 = 4, a tie at 5).  (Also measured and dropped, r06s51: the row kernel of chunk c on a second stream beside the column kernel of chunk c + 1, six chunks on
 // two buffers -- 0.27 - 0.38 TB/s against 0.35 - 0.53 in order: at these call lengths the extra launches and event waits cost more than the overlap returns.)
 // Float32 / ComplexF32 with rows of 8193 .. 16384 points, Float64 / ComplexF64 with rows of 4097 .. 9600;
 // S any size of ctbig_sizes.h, R0 any radix fft_lds.h has a butterfly for (2 .. 32): 125000 = 8 x 15625, 200000 = 16 x 12500, 2^19 = 32 x 16384.

@@ -49,26 +49,23 @@ inline bool gx_choose(int dtype, int64_t nfft, bool welch, int* R0_out, mdsp::gx
     }
     return found;
 }
-inline bool gx_size_ok(int dtype, int64_t nfft) {
+// the column factor of the split (1: one workgroup per transform; 0: no schedule), memoised per size and precision (plan creation and the plan cache's
+// key ask for it; the schedule search behind it plans every candidate split)
+inline int gx_split_r0(int dtype, int64_t nfft) {
     static std::mutex mu;
-    static std::vector<std::pair<int64_t, bool>> memo;   // (nfft << 1 | double) -> plannable
+    static std::map<int64_t, int> memo;   // (nfft << 1 | double) -> R0
     const int64_t key = (nfft << 1) | (dtype_is_double(dtype) ? 1 : 0);
     {
         std::lock_guard<std::mutex> lk(mu);
-        for (auto& e : memo)
-            if (e.first == key) return e.second;
+        if (auto it = memo.find(key); it != memo.end()) return it->second;
     }
-    const bool ok = gx_choose(dtype, nfft, true, nullptr, nullptr);
-    std::lock_guard<std::mutex> lk(mu);
-    memo.emplace_back(key, ok);
-    return ok;
-}
-
-// the column factor of the split (1: one workgroup per transform; 0: no schedule)
-inline int gx_split_r0(int dtype, int64_t nfft) {
     int R0 = 0;
-    return gx_choose(dtype, nfft, true, &R0, nullptr) ? R0 : 0;
+    if (!gx_choose(dtype, nfft, true, &R0, nullptr)) R0 = 0;
+    std::lock_guard<std::mutex> lk(mu);
+    memo.emplace(key, R0);
+    return R0;
 }
+inline bool gx_size_ok(int dtype, int64_t nfft) { return gx_split_r0(dtype, nfft) > 0; }
 
 template <typename R> int gx_prepare(GxPlan& gp, int dtype, int64_t nfft, bool welch) {
     if (gp.ready) return MDSP_OK;

@@ -11,6 +11,7 @@
 
 struct mdsp_welch_plan_s {
     int dtype = MDSP_F32, engine = MDSP_ENGINE_ROCFFT, onesided = 1;
+    int route = MDSP_ROUTE_ROCFFT, r0 = 0;   // the kernel family exec runs, decided at creation (spectral.hip choose_spectral_route)
     int64_t n = 0, noverlap = 0, nfft = 0, nout = 0;
     double r = 1;
     bool have_win = false;

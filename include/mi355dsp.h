@@ -259,6 +259,25 @@ int mdsp_stft_exec(mdsp_stft_plan plan, const void* s_dev, int64_t len, int64_t 
 int mdsp_stft_exec_host(mdsp_stft_plan plan, const void* s_host, int64_t len, int64_t nch, int64_t lds, void* out_host,
                         int64_t ldo, int64_t chs, int flags);
 
+/* Kernel family a Welch / STFT / multitaper plan runs (decided once, at plan creation, from the tunables of that moment) */
+enum {
+    MDSP_ROUTE_ROCFFT = 0,     /* the rocFFT pipeline (engine_used = MDSP_ENGINE_ROCFFT) */
+    MDSP_ROUTE_POW2 = 1,       /* register-resident power-of-two kernels (256 .. 8192 Float32, .. 4096 Float64) */
+    MDSP_ROUTE_GEN = 2,        /* mixed-radix LDS kernel and its compile-time schedules */
+    MDSP_ROUTE_GX = 3,         /* run-time-schedule single-workgroup kernel */
+    MDSP_ROUTE_CTBIG = 4,      /* Welch sums on a single-workgroup compile-time schedule */
+    MDSP_ROUTE_CTBIG_COLS = 5, /* STFT columns on a single-workgroup compile-time schedule */
+    MDSP_ROUTE_CTCOLS_BIG = 6, /* Welch sums, nfft = r0 x a compile-time row of 8193 .. 16384 points */
+    MDSP_ROUTE_CTCOLS_F64 = 7, /* Welch sums, nfft = r0 x a Float64 compile-time row of 4097 .. 9600 points */
+    MDSP_ROUTE_CTCOLS = 8,     /* Welch sums, nfft = r0 x a compile-time row (mixed-radix schedules) */
+    MDSP_ROUTE_CTROWS = 9,     /* Welch sums, nfft = r0 x S in two kernels (column kernel, then single-workgroup rows) */
+    MDSP_ROUTE_BIG = 10        /* multi-pass engine */
+};
+/* Pure host arithmetic, no device needed (like mdsp_ols_geometry_for): what mdsp_welch_plan_create (kind = 0) or mdsp_stft_plan_create /
+ * mdsp_mt_plan_create (kind = 1) WOULD record for these arguments under the current tunables -- the engine, the route (MDSP_ROUTE_*) and the
+ * column factor r0 of the CTCOLS* / CTROWS routes (0 otherwise).  Fails with the status and message plan creation would.  Any output pointer may be NULL. */
+int mdsp_spectral_route_for(int kind, int dtype, int64_t nfft, int engine, int* engine_used, int* route, int* r0);
+
 /* ------------------------------------------------------------------------------------------------------
  * 2-D periodogram (periodograms.jl:473-509, kernels fft2pow2! / fft2pow2radial! :175-232)
  *   periodogram(s::AbstractMatrix{<:Real}; nfft = (nfft1, nfft2), fs, radialsum, radialavg) of a real (n1, n2) matrix:

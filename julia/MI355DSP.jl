@@ -643,6 +643,13 @@ mutable struct StftPlan
         o
     end
 end
+# the kernel family a Welch (kind 0) or STFT / multitaper (kind 1) plan of this size would record, without a plan or a device (route: MDSP_ROUTE_* of
+# include/mi355dsp.h; r0: the column factor of the R0 x row routes, else 0)
+function spectral_route_for(kind::Integer, ::Type{T}, nfft::Integer, engine::Integer=ENGINE_AUTO) where {T}
+    eng, route, r0 = Ref{Cint}(0), Ref{Cint}(0), Ref{Cint}(0)
+    check(ccall((:mdsp_spectral_route_for, lib), Cint, (Cint, Cint, Int64, Cint, Ref{Cint}, Ref{Cint}, Ref{Cint}), kind, mdtype(T), nfft, engine, eng, route, r0))
+    (engine = Int(eng[]), route = Int(route[]), r0 = Int(r0[]))
+end
 function stft(s::Union{AbstractVecOrMat{T},DeviceArray{T}}, n::Int=size(s, 1) >> 3, noverlap::Int=n >> 1, psdonly::Bool=false;
               onesided::Bool=T <: Real, nfft::Int=nextfastfft(n), fs::Real=1, window=nothing, engine=ENGINE_AUTO, pinned::Bool=false) where {T}
     onesided && T <: Complex && throw(ArgumentError("cannot compute one-sided FFT of a complex signal"))
