@@ -22,17 +22,23 @@ The collective goes through the library's own communicator (mdsp_comm_* / mdsp_w
 entry points a Julia host binds); torch.distributed ("nccl" = RCCL) carries the bootstrap id, the barrier and the max-over-ranks
 of the timing, and is the fallback transport should the library communicator fail to initialise (reported in `config.collective`).
 
-The JSON line also carries
-    roofline      the dominant kernel: algorithmic bytes / its mean launch duration, measured live with HIP events on
-                  the launch stream; `traffic` = HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes -- measured
-                  live by re-running this script under rocprofv3 (N = 1, rocprofv3 on PATH), else the committed profiles/pmc_latest.json;
-                  `traffic_source` says which.
-    kernels       the other kernel of the step, the float4 copy / read yardsticks, and (N = 1) the remaining SURVEY section-8 rows at their
-                  single-GPU shares: stft, spectrogram, resample, firarb -- each with ms, algorithmic GB/s and frac of 8 TB/s.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the JSON line; besides the headline it carries only what
+the timed steps measured themselves:
+    roofline      the dominant kernel: algorithmic bytes / its mean launch duration, from the HIP events the timed steps recorded
+                  on the launch stream; `traffic` = HBM bytes per launch from the committed profiles/pmc_latest.json (`traffic_source` says so).
+    kernels       (filtwelch) the other kernel of the step, from the same events.
+
+--full also measures and checks everything else, each in runs of its own after the timed steps:
+    roofline      `traffic` measured live by re-running this script under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (N = 1, rocprofv3 on PATH;
+                  else the committed file, as in a plain run); `traffic_source` says which.
+    kernels       the float4 copy / read yardsticks, and (N = 1) the remaining SURVEY section-8 rows at their single-GPU shares: stft,
+                  spectrogram, resample, firarb, ... -- each with ms and frac of 8 TB/s.
     host_path     (N = 1) the host-pointer entry points (mdsp_{ols,welch,stft,fir}_exec_host: three-stage H2D || kernel || D2H pipeline): PCIe-inclusive
                   rates on a bounded sample, reported SEPARATELY -- never part of `value`.
     cpu_baseline  the CPU oracle (numpy/scipy restatement of DSP.jl's algorithm; kind "port") timed on a bounded sample: 1 thread
                   (`value`), all cores (`multi`), and the line-faithful per-block loop (`faithful`).
+    config.collective_check   the step's collective against an all_gather over a different transport (exit code 3 when they disagree).
+The --no-* options below leave single parts of that out of a --full run.
 
 --dump-outputs DIR writes what the last timed step computed on rank 0 -- filt.npy, welch_power.npy, welch_mean.npy / stft.npy / resample.npy,
 resample_avg.npy -- with a fixed, seeded sample of the outputs too large for 64 MB.  The inputs are seeded, so the same arguments give the same
@@ -65,12 +71,15 @@ def parse():
     ap.add_argument("--config", choices=["filtwelch", "stft", "resample"], default="filtwelch")
     ap.add_argument("--log2n", type=int, default=0, help="samples per channel = 2^log2n (default: 30 / 26 / 28 by config, BASELINE sizes)")
     ap.add_argument("--engine", choices=["auto", "fused", "rocfft"], default="auto")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the live PMC passes, the copy yardsticks, the other section-8 rows, the host-pointer path, "
+                         "the CPU baseline and the collective self-check (a plain run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-log2n", type=int, default=29, help="CPU baseline sample = 2^k samples")
-    ap.add_argument("--no-rows", action="store_true", help="skip the other section-8 rows (kernels.stft / spectrogram / resample / firarb)")
-    ap.add_argument("--no-host", action="store_true", help="skip the host-pointer (PCIe-inclusive) measurement")
+    ap.add_argument("--no-rows", action="store_true", help="--full without the other section-8 rows (kernels.stft / spectrogram / resample / firarb)")
+    ap.add_argument("--no-host", action="store_true", help="--full without the host-pointer (PCIe-inclusive) measurement")
     ap.add_argument("--host-log2n", type=int, default=28)
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not re-run under rocprofv3 for roofline.traffic")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full without the rocprofv3 re-runs for roofline.traffic")
     ap.add_argument("--describe-rows", action="store_true", help="print what every row of `kernels` runs (ROW_INFO) and exit")
     ap.add_argument("--dry", action="store_true", help="CPU dry mode (tests): gloo, no device work; exercises sharding, the collective and the JSON schema")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -376,8 +385,9 @@ def committed_traffic():
 
 
 def live_traffic(args):
-    """Re-run this script (2 steps, no extras) under rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, kernel-trace only, as
-    MI355X_MICROARCH.md prescribes) and return HBM bytes per launch of the fused kernels.  FETCH_SIZE is doubled (gfx950 correction)."""
+    """Re-run this script (--full: 2 steps, the yardsticks and the rows, whose markers cut the dispatch list) under rocprofv3 --pmc FETCH_SIZE and
+    --pmc WRITE_SIZE (separate passes, kernel-trace only, as MI355X_MICROARCH.md prescribes) and return HBM bytes per launch of the fused kernels.
+    FETCH_SIZE is doubled (gfx950 correction)."""
     import shutil
     import tempfile
     if shutil.which("rocprofv3") is None:
@@ -390,7 +400,7 @@ def live_traffic(args):
     for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
         d = os.path.join(tmp, ctr)
         cmd = ["rocprofv3", "--kernel-trace", "--pmc", ctr, "-d", d, "-o", "bench", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2",
-               "--warmup", "1", "--no-cpu-baseline", "--no-host", "--no-live-pmc", "--config", args.config, "--engine", args.engine] + (["--no-rows"] if args.no_rows else [])
+               "--warmup", "1", "--full", "--no-cpu-baseline", "--no-host", "--no-live-pmc", "--config", args.config, "--engine", args.engine] + (["--no-rows"] if args.no_rows else [])
         try:
             p = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
             try:
@@ -979,10 +989,12 @@ def main():
     if args.dump_outputs and rank == 0:                           # before the yardsticks below reuse the step's buffers
         dump_outputs(args.dump_outputs, outs())
 
-    # self-check of the step's collective (outside the timed region): every rank's contribution is gathered over a DIFFERENT transport
+    # --full: self-check of the step's collective (outside the timed region): every rank's contribution is gathered over a DIFFERENT transport
     # (torch.distributed all_gather), summed in Float64 on each rank, and compared with what the step's own all-reduce left behind
     collective_check, collective_failed = "n/a (no collective on this path)", False
-    if coll is not None:
+    if coll is not None and not args.full:
+        collective_check = "not run (--full checks it)"
+    elif coll is not None:
         contrib, result, div = coll()
         if world > 1:
             parts = [torch.empty_like(contrib) for _ in range(world)]
@@ -1010,7 +1022,7 @@ def main():
                        "collective_check": collective_check, f"stage_ms_{names[0]}": round(t_a, 4), f"stage_ms_{names[1].split()[0]}": round(t_b, 4)},
         }
         traffic, traffic_source = committed_traffic()
-        if world == 1 and not args.no_live_pmc:
+        if args.full and world == 1 and not args.no_live_pmc:
             try:
                 live, src = live_traffic(args)
             except Exception as e:  # pragma: no cover
@@ -1036,6 +1048,7 @@ def main():
                 kernels["other"]["valu_frac"] = other["valu_frac"]
             main_roof["other_kernel_ms"] = round(min(t_a, t_b), 4)
             main_roof["other_kernel_frac"] = kernels["other"]["frac"]
+        if args.full and args.config == "filtwelch":
             # on-box yardsticks: float4 copy (2 x 4 GiB moved), read-only stream, and the best 1:1 copy this box does (nontemporal float4, four workgroups per CU)
             nb = units_per_rank * 4
             mark("yardsticks")
@@ -1054,7 +1067,7 @@ def main():
             kernels["read_nt_GBps"] = round(nb / med / 1e6, 1)
         out["roofline"] = main_roof
         out["traffic_source"] = traffic_source
-        if world == 1 and not args.no_rows and args.config == "filtwelch":
+        if args.full and world == 1 and not args.no_rows and args.config == "filtwelch":
             del x, y
             torch.cuda.empty_cache()
             try:
@@ -1069,12 +1082,12 @@ def main():
             except Exception as e:  # pragma: no cover
                 kernels["rows_error"] = str(e)
         out["kernels"] = kernels
-        if world == 1 and not args.no_host and args.config == "filtwelch":
+        if args.full and world == 1 and not args.no_host and args.config == "filtwelch":
             try:
                 out["host_path"] = measure_host_path(lib, _lib, d, args.host_log2n)
             except Exception as e:  # pragma: no cover
                 out["host_path"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.cpu_log2n) if args.config == "filtwelch" else cpu_baseline_config(args.config, min(args.cpu_log2n, 23))
             except Exception as e:  # pragma: no cover

@@ -11,7 +11,7 @@ REPO="$(pwd)"
 OUT="$REPO/gpurun_out"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --no-cpu-baseline --no-live-pmc --no-host"   # the step kernels AND the section-8 rows (stft, spectrogram, resample, firarb) in one process
+BENCH="python $REPO/bench.py --full --no-cpu-baseline --no-live-pmc --no-host"   # the step kernels AND the section-8 rows (stft, spectrogram, resample, firarb) in one process
 rm -rf "$OUT"/prof_stats "$OUT"/prof_FETCH_SIZE "$OUT"/prof_WRITE_SIZE "$OUT"/prof_sq
 timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/prof_stats" -o bench -- $BENCH --steps 10 --warmup 3 > "$OUT/prof_stats.log" 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -31,10 +31,10 @@ python tools/prof_summary.py --rows "$(find "$OUT/prof_sq" -name '*.db' | head -
 head -30 "$OUT/kernel_stats.txt"; cat "$OUT/pmc_brief.txt"
 # the rocpd databases stay on the box (gpurun copies back at most 64 MiB): the summaries above are what profiles/ keeps
 rm -rf "$OUT"/prof_stats "$OUT"/prof_FETCH_SIZE "$OUT"/prof_WRITE_SIZE "$OUT"/prof_sq
-# the un-profiled lines of the same snapshot: the driver's command, and the two 8-GPU configs at their single-GPU shares
-python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
-python bench.py --config stft > "$OUT/bench_config4.json" 2> /dev/null
-python bench.py --config resample > "$OUT/bench_config5.json" 2> /dev/null
+# the un-profiled --full lines of the same snapshot: the headline with everything else it measures, and the two 8-GPU configs at their single-GPU shares
+python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_line.err"
+python bench.py --full --config stft > "$OUT/bench_config4.json" 2> /dev/null
+python bench.py --full --config resample > "$OUT/bench_config5.json" 2> /dev/null
 # RULE: this script is the LAST GPU session of a round -- `git rev-parse HEAD > .build_commit` before sending the snapshot, no kernel
 # commit after it.  Every summary carries that hash.
 python - <<'PY'

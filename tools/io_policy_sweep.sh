@@ -6,7 +6,7 @@
 for tag in "" nts ntls ""; do
   export MDSP_LIB_TAG=$tag
   echo "== lib tag '${tag}'"
-  timeout 100 python bench.py --no-cpu-baseline --steps 10 --warmup 3 2>&1 | python3 -c "
+  timeout 100 python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 2>&1 | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):
