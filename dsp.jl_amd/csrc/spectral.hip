@@ -1627,12 +1627,13 @@ int welch_launch_n(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st) {
                 done = true;
                 //                                              R  N  E   G  TW PAD MINW NBUF
                 // product builds: 18 (the round-2 form: identity lanes, pad 5), 30 (welch_half3_kernel, the default below the hand-allocated kernel's stream
-                // length) and 43 (mdsp_welch_w64c_asm, the default); every other variant lost its A/B (HISTORY.md section 4.3) and is built with -DMDSP_DEBUG_KNOBS only
+                // length), 43 (mdsp_welch_w64c_asm) and 44 (mdsp_welch_w64d_asm, the default); every other variant lost its A/B (HISTORY.md section 4.3) and
+                // is built with -DMDSP_DEBUG_KNOBS only
                 if (pl->variant == 18) rc = welch_run_half<R, N, EH, GH, 1, 5, 2, 1, false>(pl, a, st, &nslices);   // identity lanes, pad 5
                 else if (pl->variant == 30) rc = welch_run_half3<N, 5, 1>(pl, a, st, &nslices);   // round 3: paired samples, branch-free, window in the first stage
-                else if (pl->variant == 43) {   // ... the same, hand-allocated, shared half-frame carried (csrc/welch_w64c_asm.s): reduces into pl->reduced itself
-                    bool handled = false;
-                    rc = w64::welch_run_w64asm(pl, a, st, &handled);
+                else if (pl->variant == 43 || pl->variant == 44) {   // ... the same, hand-allocated, shared half-frame carried (csrc/welch_w64c_asm.s, and
+                    bool handled = false;                             // csrc/welch_w64d_asm.s with folded twiddles): reduces into pl->reduced itself
+                    rc = w64::welch_run_w64asm(pl, a, st, &handled, pl->variant);
                     if (rc == MDSP_OK && handled) goto reduced_done;
                 }
 #ifdef MDSP_DEBUG_KNOBS
@@ -1676,9 +1677,11 @@ int welch_launch_n(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st) {
                     // (csrc/welch_w64c_asm.s = variant 43, the form that carries the shared half-frame: 1.00 against 1.17 ms on an all-zero stream,
                     // 1.22 against 1.34 under the power cap, HBM traffic 1.01 x algorithmic; profiles/r04_welch_carry_power.json; variant 42 is the
                     // first form, which re-reads that half-frame); MDSP_WELCH_VARIANT=30 keeps welch_half3_kernel.
+                    // Round 7: csrc/welch_w64d_asm.s = variant 44, variant 43 with 13 % fewer vector instructions (folded twiddles): 1.275 against 1.356 ms, the stage
+                    // -5.1 %, filt +1.0 % in the same steps (profiles/r07_welch_w64d_ab.json); 43 stays selectable.
                     if (a.K / 2 >= (int64_t)device_cu_count() * 8 && tunables().runs_per_slot == 1) {
                         bool handled = false;
-                        rc = w64::welch_run_w64asm(pl, a, st, &handled);
+                        rc = w64::welch_run_w64asm(pl, a, st, &handled, 44);
                         if (rc == MDSP_OK && handled) goto reduced_done;
                         if (rc != MDSP_OK) return rc;
                     }

@@ -376,18 +376,23 @@ inline int welch_run_w64(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int
 
 #endif   // MDSP_DEBUG_KNOBS
 
-// ---- the hand-allocated forms: csrc/welch_w64c_asm.s (variant 43, the default: tools/gen_welch_asm_c.py) and csrc/welch_w64_asm.s (variant 42:
-// tools/gen_welch_asm.py) -----------------------------------------------------------------------------------------------------------------------------
+// ---- the hand-allocated forms: csrc/welch_w64d_asm.s (variant 44, the default: tools/gen_welch_asm_d.py), csrc/welch_w64c_asm.s (variant 43:
+// tools/gen_welch_asm_c.py) and csrc/welch_w64_asm.s (variant 42: tools/gen_welch_asm.py) ---------------------------------------------------------------
 // Same transform as welch_w64b_kernel (two waves per SIMD, two-level twiddles, direct loads) with every register assigned by the generator: all 256
 // VGPRs, no spill, 1770-1790 instructions per unit.  Variant 43 keeps the half-frame two consecutive units share in registers (twiddles in LDS, compact
 // operand banks, a two-unit loop body: 64 loads per unit, HBM traffic 1.01 x algorithmic); variant 42 loads it again (96 loads, 1.32 x).  The code
 // objects are assembled by build.py and embedded as byte arrays (*_co.h in the object directory), loaded once per device with hipModuleLoadData.
 // Host side of their contract:
-//   * a prepared per-plan block: window pairs (w[p], w[p + N/2]) as Float32 (16 KiB) + the per-lane twiddles W^{8 lane j}, W^{lane j}, j = 1..7;
+//   * a prepared per-plan block: window pairs (w[p], w[p + N/2]) as Float32 (16 KiB) + the per-lane twiddles W^{8 lane j}, W^{lane j}, j = 1..7
+//     (28 floats per lane), then for variant 44 sixteen rows of 64 pairs: W^{m}, W^{2m}, W^{4m}, W^{m + N/8}, m = lane + 64 k1, k1 = 0..3;
 //   * Float32 partial rows part[((slot nch + ch) nflush + f) N + bin]: a wave with U units writes exactly ceil(U / 128) of its nflush rows, the row
 //     reduction skips the others (no zeroing);
 //   * the units they run all have both frames; the odd last frame of a channel goes through welch_half3_kernel and is added to the same sums.
 #include "welch_w64c_asm_co.h"   // static const unsigned char welch_w64c_asm_co[]; generated by build.py from welch_w64c_asm.s (tools/gen_welch_asm_c.py)
+// Variant 44 (csrc/welch_w64d_asm.s) is variant 43 with 13 % fewer vector instructions per unit (1306 against 1506): FMA-folded twiddled butterflies,
+// one factored twiddle for pass B's second layer and packed power sums (tools/gen_welch_asm_d.py); the kernel runs at the package power cap, so its
+// time follows them: 1.275 against 1.356 ms (profiles/r07_welch_w64d_ab.json).
+#include "welch_w64d_asm_co.h"
 // (variant 42, csrc/welch_w64_asm.s -- the first hand-allocated form, which re-read the shared half-frame: 1.32 x the algorithmic bytes -- was removed in round 5;
 // its generator tools/gen_welch_asm.py stays: gen_welch_asm_c.py builds on its scheduler, allocator and emulator)
 
@@ -415,6 +420,16 @@ __global__ __launch_bounds__(256) void w64asm_prepare_kernel(const double* __res
             tw[2 * (j - 1) + 1] = a.y;
             tw[14 + 2 * (j - 1)] = b.x;
             tw[14 + 2 * (j - 1) + 1] = b.y;
+        }
+        // ... and behind all of those, for variant 44: 16 rows of 64 pairs, row 4 k1 + q (k1 = 0..3) = W^{m}, W^{2m}, W^{4m}, W^{m + N/8}, m = lane + 64 k1
+        for (int k1 = 0; k1 < 4; ++k1) {
+            const int m = i + 64 * k1;
+            const int e[4] = {m, 2 * m, 4 * m, m + N / 8};
+            for (int q = 0; q < 4; ++q) {
+                const cx<float> w = table[e[q] & (N - 1)];
+                out[2 * HALF + 28 * 64 + 128 * (4 * k1 + q) + 2 * i] = w.x;
+                out[2 * HALF + 28 * 64 + 128 * (4 * k1 + q) + 2 * i + 1] = w.y;
+            }
         }
     }
 }
@@ -470,31 +485,31 @@ struct W64AsmModule {
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
 };
-// carry: mdsp_welch_w64c_asm (the shared half-frame of consecutive units stays in registers: 64 loads per unit, 1.0 x the algorithmic bytes) instead
-// of mdsp_welch_w64_asm (96 loads, 1.32 x)
-inline int w64asm_function(hipFunction_t* fn, bool carry) {
+// the two carried-half-frame forms (the shared half-frame of consecutive units stays in registers: 64 loads per unit, 1.0 x the algorithmic bytes):
+// variant 44 mdsp_welch_w64d_asm (folded twiddles, the default) or variant 43 mdsp_welch_w64c_asm
+inline int w64asm_function(hipFunction_t* fn, int variant) {
+    if (variant != 43 && variant != 44) MDSP_FAIL(MDSP_ERR_ARGUMENT, "no hand-allocated Welch kernel for variant %d", variant);
     static std::mutex mu;
     static W64AsmModule mods[2][64];
     int dev = 0;
     MDSP_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(mu);
-    W64AsmModule& m = mods[carry ? 1 : 0][dev & 63];
+    W64AsmModule& m = mods[variant - 43][dev & 63];
     if (!m.fn) {
-        (void)carry;
-        MDSP_HIP(hipModuleLoadData(&m.mod, welch_w64c_asm_co));
-        MDSP_HIP(hipModuleGetFunction(&m.fn, m.mod, "mdsp_welch_w64c_asm"));
+        MDSP_HIP(hipModuleLoadData(&m.mod, variant == 44 ? welch_w64d_asm_co : welch_w64c_asm_co));
+        MDSP_HIP(hipModuleGetFunction(&m.fn, m.mod, variant == 44 ? "mdsp_welch_w64d_asm" : "mdsp_welch_w64c_asm"));
     }
     *fn = m.fn;
     return MDSP_OK;
 }
 
 // returns MDSP_OK with *handled = true when the sums have been added to pl->reduced (the caller skips its own slice reduction)
-template <int DUMMY = 0> int welch_run_w64asm(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, bool* handled, bool carry = true) {
+template <int DUMMY = 0> int welch_run_w64asm(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, bool* handled, int variant = 44) {
     *handled = false;
     hipFunction_t fn = nullptr;
-    MDSP_TRY(w64asm_function(&fn, carry));
+    MDSP_TRY(w64asm_function(&fn, variant));
     // the prepared block (per plan: the window and the root table never change)
-    constexpr size_t PREP_FLOATS = 2 * HALF + 28 * 64;
+    constexpr size_t PREP_FLOATS = 2 * HALF + 28 * 64 + 16 * 128;
     if (pl->w64prep.bytes == 0) {
         MDSP_TRY(pl->w64prep.reserve(PREP_FLOATS * sizeof(float)));
         hipLaunchKernelGGL(w64asm_prepare_kernel, dim3(HALF / 256), dim3(256), 0, st, a.win, a.n, static_cast<const cx<float>*>(a.table), pl->w64prep.as<float>());

@@ -50,9 +50,53 @@ class GenC(W.Gen):
     BANK = (68, 100)     # two banks of 16 pairs: value e of a half-frame's 32 per lane sits in 32-bit register BANK[b] + e
     HH0 = 132            # H1 as pairs, as in gen_welch_asm.py
 
+    NAME = NAME
+    SCRIPT = "tools/gen_welch_asm_c.py"
+    LDS_BYTES = LDS_BYTES
+    WIN_OFF = WIN_OFF
+    XB_OFF = XB_OFF
+
     def __init__(self, parity):
         super().__init__()
         self.parity = parity
+
+    @staticmethod
+    def tw_rows(lane):
+        """the per-lane twiddle rows in LDS (row r at byte 512 r): W^(8 lane j), then W^(lane j), j = 1..7"""
+        roots = np.exp(-2j * np.pi * np.arange(N) / N)
+        return [roots[(8 * lane * j) % N] for j in range(1, 8)] + [roots[(lane * j) % N] for j in range(1, 8)]
+
+    @classmethod
+    def emit_tw_prologue(cls, A):
+        """global -> LDS: the window pairs (v3 = tid * 32) and the twiddle rows"""
+        A("\tv_mul_u32_u24_e32 v4, 112, v1                ; per-lane twiddles: 28 floats at tw + lane * 112")
+        for k in range(7):
+            A(f"\tglobal_load_dwordx4 v[{cls.POOL0 + 4 * k}:{cls.POOL0 + 4 * k + 3}], v4, s[10:11] offset:{16 * k}")
+        A("\tv_lshlrev_b32_e32 v7, 3, v1                  ; lane * 8")
+        A("\ts_waitcnt vmcnt(7)")
+        A(f"\tds_write_b128 v3, v[8:11] offset:{WIN_OFF}")
+        A(f"\tds_write_b128 v3, v[12:15] offset:{WIN_OFF + 16}")
+        A("\ts_waitcnt vmcnt(0)")
+        for k in range(14):
+            A(f"\tds_write_b64 v7, v[{cls.POOL0 + 2 * k}:{cls.POOL0 + 2 * k + 1}] offset:{512 * k}      ; every wave writes the same 14 rows")
+
+    def sconsts(self):
+        return W.sconsts(self)
+
+    def acc_reg(self, s):
+        """the 32-bit accumulator register of v[s] (bin lane + 64 kt sits in v[slot64(kt)])"""
+        return self.ACC0 + s
+
+    def emit_sconsts(self, A, fbits):
+        h = np.float32(math.sqrt(0.5))
+        A(f"\ts_mov_b32 s{self.S_HH}, {fbits(h)}")
+        A(f"\ts_mov_b32 s{self.S_HH + 1}, {fbits(h)}")
+        A(f"\ts_mov_b32 s{self.S_PM}, {fbits(1.0)}")
+        A(f"\ts_mov_b32 s{self.S_PM + 1}, {fbits(-1.0)}")
+        for m, p in self.wexp.items():
+            c, s_ = W.w64(m)
+            A(f"\ts_mov_b32 s{p}, {fbits(c)}                   ; W64^{m}")
+            A(f"\ts_mov_b32 s{p + 1}, {fbits(s_)}")
 
     def cval(self, bank, e):
         return ("h", self.BANK[bank] + 2 * (e // 2), e % 2)
@@ -229,35 +273,38 @@ class EmuC(W.Emu):
                 super().run([ins])
 
 
-def build():
-    gA, gB = GenC(0), GenC(1)
-    return gA, gB, gA.build_unit(), gB.build_unit(), GenC(0).build_first_loads()
+def build(G=GenC):
+    gA, gB = G(0), G(1)
+    return gA, gB, gA.build_unit(), gB.build_unit(), G(0).build_first_loads()
 
 
-def check():
+def valu_count(body):
+    """vector ALU instructions of a unit body (packed and scalar arithmetic, lane swaps): what the kernel's time follows under the power cap"""
+    return sum(1 for i in body if i.op.startswith("v_"))
+
+
+def check(G=GenC):
     rng = np.random.default_rng(1776)
-    gA, gB, bodyA, bodyB, loads = build()
+    gA, gB, bodyA, bodyB, loads = build(G)
     nunits = 5
     sig = rng.standard_normal((nunits + 3) * N).astype(np.float32)
     win = (0.5 - 0.5 * np.cos(2 * np.pi * np.arange(N) / (N - 1))).astype(np.float32)
-    em = EmuC(gA, W.sconsts(gA))
-    em.lds = np.zeros(LDS_BYTES // 4, dtype=np.float32)
+    em = EmuC(gA, gA.sconsts())
+    em.lds = np.zeros(G.LDS_BYTES // 4, dtype=np.float32)
     lane = np.arange(64)
     em.vi[gA.V_OFF] = lane * 4
     em.vi[gA.V_WIN] = lane * 8
     wave = 5
-    xb = XB_OFF + wave * XBUF_BYTES
+    xb = G.XB_OFF + wave * XBUF_BYTES
     em.vi[gA.V_XW] = xb + ((lane >> 5) * 32 + (lane & 31)) * XROW * 8
     em.vi[gA.V_XR] = xb + ((lane >> 5) * 32) * XROW * 8 + (lane & 31) * 8
-    wl = em.lds[WIN_OFF // 4: (WIN_OFF + W.WIN_BYTES) // 4].reshape(HALF, 2)
+    wl = em.lds[G.WIN_OFF // 4: (G.WIN_OFF + W.WIN_BYTES) // 4].reshape(HALF, 2)
     wl[:, 0] = win[:HALF]
     wl[:, 1] = win[HALF:]
-    roots = np.exp(-2j * np.pi * np.arange(N) / N)
-    twl = em.lds[: TW_BYTES // 4].reshape(14, 64, 2)
-    for j in range(1, 8):
-        wa, wb = roots[(8 * lane * j) % N], roots[(lane * j) % N]
-        twl[j - 1, :, 0], twl[j - 1, :, 1] = wa.real, wa.imag
-        twl[7 + j - 1, :, 0], twl[7 + j - 1, :, 1] = wb.real, wb.imag
+    rows = G.tw_rows(lane)
+    twl = em.lds[: 128 * len(rows)].reshape(len(rows), 64, 2)
+    for r, w in enumerate(rows):
+        twl[r, :, 0], twl[r, :, 1] = w.real, w.imag
     em.glob = sig
     ref = np.zeros(N)
     em.v[gA.POOL0:] = np.float32(np.nan)
@@ -271,7 +318,7 @@ def check():
         ref += np.abs(np.fft.fft(win.astype(np.float64) * (a + 1j * b))) ** 2
     got = np.zeros(N)
     for kt in range(64):
-        got[lane + 64 * kt] = em.v[gA.ACC0 + slot64(kt)]
+        got[lane + 64 * kt] = em.v[gA.acc_reg(slot64(kt))]
     err = np.linalg.norm(got - ref) / np.linalg.norm(ref)
     worst = np.max(np.abs(got - ref) / ref.max())
     kinds = {}
@@ -279,15 +326,16 @@ def check():
         kinds[i.op] = kinds.get(i.op, 0) + 1
     nins = sum(v for k, v in kinds.items() if k != "comment")
     nbad = W.verify_waits(loads + bodyA + bodyB + bodyA + bodyB)
-    print(f"emulated {nunits} units (A B A B A): relerr {err:.3e}, worst bin / max {worst:.3e}; {nins} instructions per unit, peak live pairs {gA.maxlive} / {gB.maxlive} of "
+    print(f"emulated {nunits} units (A B A B A): relerr {err:.3e}, worst bin / max {worst:.3e}; {nins} instructions per unit ({valu_count(bodyA)} / {valu_count(bodyB)} vector ALU), "
+          f"peak live pairs {gA.maxlive} / {gB.maxlive} of "
           f"{gA.NPOOL}, scheduler stall slots {gA.stalls} / {gB.stalls}, {gA.loads_in_body} / {gB.loads_in_body} of 64 loads inside the body, wait check: {nbad} problems")
     print("  ", {k: v for k, v in sorted(kinds.items()) if k != "comment"})
     return err < 2e-6 and nbad == 0
 
 
-def kernel_text():
-    gA, gB, bodyA, bodyB, loads = build()
-    G = GenC
+def kernel_text(G=GenC):
+    gA, gB, bodyA, bodyB, loads = build(G)
+    NAME = G.NAME
     L = []
     A = L.append
     A('\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"')
@@ -298,7 +346,7 @@ def kernel_text():
     A("\t.p2align\t8")
     A(f"\t.type\t{NAME},@function")
     A(f"{NAME}:")
-    A("; generated by tools/gen_welch_asm_c.py -- do not edit")
+    A(f"; generated by {G.SCRIPT} -- do not edit")
     A("\ts_load_dwordx8 s[4:11], s[0:1], 0x0          ; s, part, winpairs, tw")
     A("\ts_load_dwordx8 s[12:19], s[0:1], 0x20        ; lds_, units, run_len, nch")
     A("\ts_load_dword s20, s[0:1], 0x40               ; nflush")
@@ -311,23 +359,14 @@ def kernel_text():
     A("\tv_lshlrev_b32_e32 v3, 5, v0                  ; tid * 32: window pairs, 16 KiB global -> LDS behind the twiddle rows")
     A("\tglobal_load_dwordx4 v[8:11], v3, s[8:9]")
     A("\tglobal_load_dwordx4 v[12:15], v3, s[8:9] offset:16")
-    A("\tv_mul_u32_u24_e32 v4, 112, v1                ; per-lane twiddles: 28 floats at tw + lane * 112")
-    for k in range(7):
-        A(f"\tglobal_load_dwordx4 v[{G.POOL0 + 4 * k}:{G.POOL0 + 4 * k + 3}], v4, s[10:11] offset:{16 * k}")
-    A("\tv_lshlrev_b32_e32 v7, 3, v1                  ; lane * 8")
-    A("\ts_waitcnt vmcnt(7)")
-    A(f"\tds_write_b128 v3, v[8:11] offset:{WIN_OFF}")
-    A(f"\tds_write_b128 v3, v[12:15] offset:{WIN_OFF + 16}")
-    A("\ts_waitcnt vmcnt(0)")
-    for k in range(14):
-        A(f"\tds_write_b64 v7, v[{G.POOL0 + 2 * k}:{G.POOL0 + 2 * k + 1}] offset:{512 * k}      ; every wave writes the same 14 rows")
+    G.emit_tw_prologue(A)
     A("\ts_waitcnt lgkmcnt(0)")
     A("\ts_barrier")
     A(f"\tv_lshlrev_b32_e32 v{G.V_OFF}, 2, v1               ; lane * 4")
     A("\tv_lshrrev_b32_e32 v5, 5, v1                  ; lane >> 5")
     A("\tv_and_b32_e32 v6, 31, v1                     ; lane & 31")
     A(f"\ts_mul_i32 s22, s21, {XBUF_BYTES}")
-    A(f"\ts_add_i32 s22, s22, {XB_OFF}                ; this wave's exchange buffer")
+    A(f"\ts_add_i32 s22, s22, {G.XB_OFF}                ; this wave's exchange buffer")
     A("\tv_lshl_add_u32 v7, v5, 5, v6                 ; (lane >> 5) * 32 + (lane & 31)")
     A(f"\tv_mul_u32_u24_e32 v7, {XROW * 8}, v7")
     A(f"\tv_add_u32_e32 v{G.V_XW}, s22, v7")
@@ -339,19 +378,11 @@ def kernel_text():
         A(f"\tv_mov_b32_e32 v{G.ACC0 + s}, 0")
     for k in range(5):
         A(f"\ts_mov_b32 s{G.S_K4 + k}, {4096 * (k + 1)}")
-    h = np.float32(math.sqrt(0.5))
 
     def fbits(x):
         return "0x%08x" % int(np.float32(x).view(np.uint32))
 
-    A(f"\ts_mov_b32 s{G.S_HH}, {fbits(h)}")
-    A(f"\ts_mov_b32 s{G.S_HH + 1}, {fbits(h)}")
-    A(f"\ts_mov_b32 s{G.S_PM}, {fbits(1.0)}")
-    A(f"\ts_mov_b32 s{G.S_PM + 1}, {fbits(-1.0)}")
-    for m, p in gA.wexp.items():
-        c, s_ = W.w64(m)
-        A(f"\ts_mov_b32 s{p}, {fbits(c)}                   ; W64^{m}")
-        A(f"\ts_mov_b32 s{p + 1}, {fbits(s_)}")
+    gA.emit_sconsts(A, fbits)
     A("\ts_lshl_b32 s22, s2, 3")
     A("\ts_add_u32 s22, s22, s21                      ; slot")
     A("\ts_mul_i32 s23, s22, s16                      ; u0 = slot * run_len")
@@ -393,7 +424,7 @@ def kernel_text():
         for kt in range(64):
             k, imm = divmod(256 * kt, 4096)
             so = "0" if k == 0 else f"s{G.S_K4 + k - 1}"
-            A(f"\tbuffer_store_dword v{G.ACC0 + slot64(kt)}, v{G.V_OFF}, s[28:31], {so} offen offset:{imm}")
+            A(f"\tbuffer_store_dword v{gA.acc_reg(slot64(kt))}, v{G.V_OFF}, s[28:31], {so} offen offset:{imm}")
         A("\ts_add_u32 s28, s28, 0x4000")
         A("\ts_addc_u32 s29, s29, 0")
         A("\ts_nop 4")
@@ -430,7 +461,7 @@ def kernel_text():
     A("\t.section\t.rodata,\"a\",@progbits")
     A("\t.p2align\t6, 0x0")
     A(f"\t.amdhsa_kernel {NAME}")
-    A(f"\t\t.amdhsa_group_segment_fixed_size {LDS_BYTES}")
+    A(f"\t\t.amdhsa_group_segment_fixed_size {G.LDS_BYTES}")
     for line in ("private_segment_fixed_size 0", "kernarg_size 72", "user_sgpr_count 2", "user_sgpr_dispatch_ptr 0", "user_sgpr_queue_ptr 0",
                  "user_sgpr_kernarg_segment_ptr 1", "user_sgpr_dispatch_id 0", "user_sgpr_kernarg_preload_length 0", "user_sgpr_kernarg_preload_offset 0",
                  "user_sgpr_private_segment_size 0", "uses_dynamic_stack 0", "enable_private_segment 0", "system_sgpr_workgroup_id_x 1",
@@ -450,7 +481,7 @@ def kernel_text():
     A("      - .offset:         0")
     A("        .size:           72")
     A("        .value_kind:     by_value")
-    A(f"    .group_segment_fixed_size: {LDS_BYTES}")
+    A(f"    .group_segment_fixed_size: {G.LDS_BYTES}")
     A("    .kernarg_segment_align: 8")
     A("    .kernarg_segment_size: 72")
     A("    .language:       OpenCL C")
