@@ -115,6 +115,7 @@ PROTOTYPES = {
     "mdsp_periodogram2_exec": (ci, [vp, vp, i64, vp, i64, vp]),
     "mdsp_periodogram2_geometry_for": (ci, [i64, i64, pi64, pi64, pi64]),
     "mdsp_tdfir_state_exec": (ci, [vp, i64, ci, vp, i64, i64, i64, vp, i64, vp, vp]),
+    "mdsp_tdfir_state_exec_t": (ci, [vp, i64, ci, ci, vp, i64, i64, i64, vp, i64, vp, vp]),
     "mdsp_extrapolate": (ci, [vp, i64, i64, i64, ci, i64, vp, i64, vp]),
     "mdsp_mt_plan_create": (ci, [pvp, i64, i64, vp, i64, vp, ci, ci, ci]),
     "mdsp_mt_plan_destroy": (ci, [vp]),
@@ -156,6 +157,7 @@ PROTOTYPES = {
     "mdsp_convnd_fft": (ci, [vp, pi64, vp, pi64, ci, ci, vp, vp]),
     "mdsp_convnd_direct": (ci, [vp, pi64, vp, pi64, ci, ci, vp, vp]),
     "mdsp_tdfir_exec": (ci, [vp, i64, ci, vp, i64, i64, i64, vp, i64, vp]),
+    "mdsp_tdfir_exec_t": (ci, [vp, i64, ci, ci, vp, i64, i64, i64, vp, i64, vp]),
     "mdsp_ols_plan_cached": (ci, [pvp, vp, i64, i64, i64, ci, ci, ci, vp]),
     "mdsp_welch_plan_cached": (ci, [pvp, i64, i64, i64, pdbl, cd, ci, ci, ci, vp]),
     "mdsp_stft_plan_cached": (ci, [pvp, i64, i64, i64, pdbl, cd, ci, ci, ci, ci, vp]),

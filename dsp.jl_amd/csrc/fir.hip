@@ -31,6 +31,7 @@
 #include "devio.h"
 #include "arb_scan.h"
 #include "fir_reg.h"
+#include "fir_creg.h"
 #include "fft_lds.h"
 
 using namespace mdsp;
@@ -53,6 +54,19 @@ template <typename R> __device__ __forceinline__ void fma_acc(cx<R>& acc, R h, c
 }
 template <typename R> __device__ __forceinline__ R mul_first(R h, R x) { return h * x; }
 template <typename R> __device__ __forceinline__ cx<R> mul_first(R h, cx<R> x) { return {h * x.x, h * x.y}; }
+// complex taps (generic unsafe_dot, util.jl:225-283: the plain complex product, no conjugate): h x = h.re (x.re, x.im) + h.im (-x.im, x.re), in that order
+template <typename R> __device__ __forceinline__ void fma_acc(cx<R>& acc, cx<R> h, R x) {
+    acc.x = fma(x, h.x, acc.x);
+    acc.y = fma(x, h.y, acc.y);
+}
+template <typename R> __device__ __forceinline__ void fma_acc(cx<R>& acc, cx<R> h, cx<R> x) {
+    acc.x = fma(h.x, x.x, acc.x);
+    acc.y = fma(h.x, x.y, acc.y);
+    acc.x = fma(h.y, -x.y, acc.x);
+    acc.y = fma(h.y, x.x, acc.y);
+}
+template <typename R> __device__ __forceinline__ cx<R> mul_first(cx<R> h, R x) { return {h.x * x, h.y * x}; }
+template <typename R> __device__ __forceinline__ cx<R> mul_first(cx<R> h, cx<R> x) { return {fma(h.y, -x.y, h.x * x.x), fma(h.y, x.x, h.x * x.y)}; }
 
 // 2 a - b  (extrapolate_signal!)
 template <typename R> __device__ __forceinline__ R sub2(R a, R b) { return (R)2 * a - b; }
@@ -69,7 +83,7 @@ struct FirArgs {
     const void* x;       // (xlen, nch), ld ldx, storage type XS
     const void* hist;    // (hl, nch) storage type XS
     void* y;             // (ycap, nch), ld ldy, type A
-    const void* pfbT;    // tp * L taps (compute real type R), pfbT[i*L + phi]
+    const void* pfbT;    // tp * L taps (compute real type R, or cx<R> for complex taps), pfbT[i*L + phi]
     int64_t xlen, ldx, ldy, nout;
     int64_t phi0m1;      // phi0 - 1
     int64_t d0;          // input deficit (1-based first input index)
@@ -79,12 +93,13 @@ struct FirArgs {
     int pfb_in_lds;
 };
 
-// XS: storage type of x (float, double, cx<float>, cx<double>);  A: accumulate/output type (R or cx<R>)
-template <typename XS, typename A, typename R>
+// XS: storage type of x (float, double, cx<float>, cx<double>);  A: accumulate/output type (R or cx<R>);  Z: staged type (A for real taps; under complex
+// taps the signal's own class in the arithmetic precision, so a real signal takes half the LDS of its complex output);  H: tap type (R or cx<R>)
+template <typename XS, typename A, typename R, typename Z = A, typename H = R>
 MDSP_NO_LSO __global__ __launch_bounds__(256) void polyphase_fir_kernel(FirArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    A* zs = reinterpret_cast<A*>(smem);                                  // staged input span (converted to A)
-    R* ps = reinterpret_cast<R*>(smem + (size_t)a.span * sizeof(A));      // pfbT (optional)
+    Z* zs = reinterpret_cast<Z*>(smem);                                  // staged input span (converted to Z)
+    H* ps = reinterpret_cast<H*>(smem + (size_t)a.span * sizeof(Z));      // pfbT (optional)
     const int64_t ch = blockIdx.y;
     const int64_t m0 = (int64_t)blockIdx.x * a.tile;
     if (m0 >= a.nout) return;
@@ -99,12 +114,12 @@ MDSP_NO_LSO __global__ __launch_bounds__(256) void polyphase_fir_kernel(FirArgs 
     const int nz = (int)(z_last - z_first + 1);
     for (int k = threadIdx.x; k < nz; k += blockDim.x) {
         const int64_t zi = z_first + k;  // index into [history ; x]
-        A v{};
-        if (zi < a.hl) v = to_acc(hc[zi], (A*)nullptr);
-        else if (zi - a.hl < a.xlen) v = to_acc(xc[zi - a.hl], (A*)nullptr);
+        Z v{};
+        if (zi < a.hl) v = to_acc(hc[zi], (Z*)nullptr);
+        else if (zi - a.hl < a.xlen) v = to_acc(xc[zi - a.hl], (Z*)nullptr);
         zs[k] = v;
     }
-    const R* pf = static_cast<const R*>(a.pfbT);
+    const H* pf = static_cast<const H*>(a.pfbT);
     if (a.pfb_in_lds) {
         const int np = a.tp * a.L;
         for (int k = threadIdx.x; k < np; k += blockDim.x) ps[k] = pf[k];
@@ -116,8 +131,8 @@ MDSP_NO_LSO __global__ __launch_bounds__(256) void polyphase_fir_kernel(FirArgs 
         const int64_t p = p_first + (int64_t)j * a.M;
         const int phi = (int)(p % a.L);
         const int zoff = (int)(a.d0 + p / a.L - 1 - z_first);
-        const A* zp = zs + zoff;
-        const R* hp = pf + phi;
+        const Z* zp = zs + zoff;
+        const H* hp = pf + phi;
         A acc = mul_first(hp[0], zp[0]);
         for (int i = 1; i < a.tp; ++i) fma_acc(acc, hp[(int64_t)i * a.L], zp[i]);
         yc[m0 + j] = acc;
@@ -1443,6 +1458,7 @@ struct mdsp_fir_s {
     int64_t L = 1, M = 1, hlen = 0, tp = 0, hl = 0, nch = 1;
     int taps_dtype = MDSP_F32, x_dtype = MDSP_F32, out_dtype = MDSP_F32;
     bool acc_double = false;
+    bool ctaps = false;   // complex taps: pfbT holds cx<R>, the output is complex for every signal type; generic or complex register-tap kernel (fir_creg.hip)
     int64_t phi_idx = 1, input_deficit = 1;  // the reference's 1-based state
     DevBuf pfbT;
     DevBuf hist[2];
@@ -1471,25 +1487,25 @@ struct mdsp_firarb_s {
 
 namespace {
 
-template <typename XS, typename A, typename R> int fir_launch(mdsp_fir_s* f, FirArgs& a, hipStream_t st) {
+template <typename XS, typename A, typename R, typename Z = A, typename H = R> int fir_launch(mdsp_fir_s* f, FirArgs& a, hipStream_t st) {
     // tile size: keep the staged span + filter bank within 64 KiB of LDS
-    const int64_t pfb_bytes = (int64_t)f->tp * f->L * (int64_t)sizeof(R);
+    const int64_t pfb_bytes = (int64_t)f->tp * f->L * (int64_t)sizeof(H);
     a.pfb_in_lds = pfb_bytes <= 40 * 1024;
     int tile = 4096;
     int64_t span = 0;
     while (true) {
         span = ((int64_t)tile * f->M + f->L - 1) / f->L + f->tp + 2;
-        const int64_t bytes = span * (int64_t)sizeof(A) + (a.pfb_in_lds ? pfb_bytes : 0);
+        const int64_t bytes = span * (int64_t)sizeof(Z) + (a.pfb_in_lds ? pfb_bytes : 0);
         if (bytes <= 64 * 1024 || tile <= 64) break;
         tile /= 2;
     }
     // the smallest tile and the bank together miss the LDS (ComplexF64 decimation by 63 with 5000 taps: 144 + 40 KiB): the taps stay in L2
-    if (a.pfb_in_lds && span * (int64_t)sizeof(A) + pfb_bytes > 150 * 1024) a.pfb_in_lds = 0;
-    const int64_t lds_bytes = span * (int64_t)sizeof(A) + (a.pfb_in_lds ? pfb_bytes : 0);
+    if (a.pfb_in_lds && span * (int64_t)sizeof(Z) + pfb_bytes > 150 * 1024) a.pfb_in_lds = 0;
+    const int64_t lds_bytes = span * (int64_t)sizeof(Z) + (a.pfb_in_lds ? pfb_bytes : 0);
     if (lds_bytes > 150 * 1024) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "filter too long for the polyphase kernel (tapsPerPhase=%lld)", (long long)f->tp);
     a.tile = tile;
     a.span = (int)span;
-    auto kern = polyphase_fir_kernel<XS, A, R>;
+    auto kern = polyphase_fir_kernel<XS, A, R, Z, H>;
     if (lds_bytes > 48 * 1024) MDSP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
     const dim3 grid((unsigned)cdiv(a.nout, tile), (unsigned)f->nch);
     hipLaunchKernelGGL(kern, grid, dim3(256), (size_t)lds_bytes, st, a);
@@ -1580,7 +1596,7 @@ template <int TPC, int P> int fir_fast_launch(mdsp_fir_s* f, const FirArgs& a, h
 
 // Fast path applies to Float32 taps x real Float32 signal with <= 64 taps per phase and <= 1024 phase groups.
 bool fir_fast_ok(const mdsp_fir_s* f, int P) {
-    if (f->acc_double || f->x_dtype != MDSP_F32 || f->tp > 64) return false;
+    if (f->ctaps || f->acc_double || f->x_dtype != MDSP_F32 || f->tp > 64) return false;
     if (MDSP_DBG(fir_generic) || tunables().fir_exact || f->exact) return false;
     if (P >= 2 && (f->M > f->L || f->L < P)) return false;
     if (cdiv(f->L, P) > 256) return false;
@@ -1629,7 +1645,7 @@ FirMGeo fir_mm_geo_compute(const mdsp_fir_s* f, bool allow_regs, int rb_cap = 0)
     FirMGeo g;
     const bool t64 = allow_regs && tunables().fir_mm_t64 != 0;
     // element type: signal and compute type must agree (Float32 taps x Float32 samples, or Float64 arithmetic on Float64 samples)
-    if (f->acc_double != dtype_is_double(f->x_dtype)) return g;
+    if (f->ctaps || f->acc_double != dtype_is_double(f->x_dtype)) return g;   // (complex taps: not a matrix-core shape)
     g.esz = f->acc_double ? 8 : 4;
     g.CS = dtype_is_complex(f->x_dtype) ? 2 : 1;
     int chmax = (g.esz == 4 && g.CS == 1) ? 4 : 2;   // 16-row chunks per multiplying wave: fewer when the tile would not fit the LDS
@@ -1967,7 +1983,7 @@ struct DecGeo {
 };
 DecGeo fir_dec_geo(const mdsp_fir_s* f) {
     DecGeo g;
-    if (f->L != 1 || f->M < 2 || f->M > 64 || tunables().fir_dec == 0 || tunables().fir_exact || f->exact || MDSP_DBG(fir_generic)) return g;
+    if (f->ctaps || f->L != 1 || f->M < 2 || f->M > 64 || tunables().fir_dec == 0 || tunables().fir_exact || f->exact || MDSP_DBG(fir_generic)) return g;
     if (f->acc_double != dtype_is_double(f->x_dtype)) return g;   // Float32 samples under Float64 taps: the generic kernel converts as it stages
     // Where it wins (profiles/r05_fir_dec_ab.json, 4 channels x 2^26 samples, resample_filter taps): Float64 / ComplexF64 from M = 4 on (1.1 - 4.1x),
     // Float32 / ComplexF32 at M = 4 (1.17 - 1.19x) and from M = 8 on (1.1 - 3.9x); at M = 2, 3 and the Float32 M = 5, 6, 7 the matrix-core kernel's
@@ -2087,11 +2103,32 @@ struct FirChoiceScope {
 
 bool fir_reg_use(const mdsp_fir_s* f) {
     if (MDSP_DBG(fir_generic) || tunables().fir_exact || f->exact || f->kind == 4) return false;
+    if (f->ctaps) return fir_creg_ok(f->x_dtype, f->acc_double, f->tp, f->L, f->M);
     return fir_reg_ok(f->x_dtype, f->acc_double, f->tp, f->L, f->M);
+}
+
+// complex taps: the complex register-tap kernel where its predicate claims the shape, the generic kernel with H = cx<R> everywhere else
+int fir_dispatch_ctaps(mdsp_fir_s* f, FirArgs& a, hipStream_t st) {
+    if (fir_reg_use(f)) {
+        FirRegArgs b{};
+        b.x = a.x; b.hist = a.hist; b.y = a.y; b.pfbT = a.pfbT;
+        b.xlen = a.xlen; b.ldx = a.ldx; b.ldy = a.ldy; b.nout = a.nout;
+        b.phi0m1 = a.phi0m1; b.d0 = a.d0;
+        b.L = a.L; b.M = a.M; b.tp = a.tp; b.hl = a.hl;
+        return fir_creg_run(f->x_dtype, f->acc_double, b, f->nch, st);
+    }
+    const bool d = f->acc_double;
+    switch (f->x_dtype) {
+        case MDSP_F32: return d ? fir_launch<float, cx<double>, double, double, cx<double>>(f, a, st) : fir_launch<float, cx<float>, float, float, cx<float>>(f, a, st);
+        case MDSP_F64: return fir_launch<double, cx<double>, double, double, cx<double>>(f, a, st);
+        case MDSP_C32: return d ? fir_launch<cx<float>, cx<double>, double, cx<double>, cx<double>>(f, a, st) : fir_launch<cx<float>, cx<float>, float, cx<float>, cx<float>>(f, a, st);
+        default: return fir_launch<cx<double>, cx<double>, double, cx<double>, cx<double>>(f, a, st);
+    }
 }
 
 int fir_dispatch(mdsp_fir_s* f, FirArgs& a, hipStream_t st) {
     const FirChoiceScope choice(f);
+    if (f->ctaps) return fir_dispatch_ctaps(f, a, st);
     {
         const DecGeo dg = fir_dec_geo(f);
         if (dg.ok) return fir_dec_dispatch(f, a, dg, st);
@@ -2150,7 +2187,7 @@ int mdsp_fir_create(mdsp_fir* fo, const void* taps_host, int64_t hlen, int64_t L
     *fo = nullptr;
     if (!taps_host || hlen < 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "filter taps must be non-empty");
     if (L < 1 || M < 1) MDSP_FAIL(MDSP_ERR_DOMAIN, "resampling ratio must be positive");
-    if (taps_dtype != MDSP_F32 && taps_dtype != MDSP_F64) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "only real Float32/Float64 taps are supported on the device");
+    if (!dtype_valid(taps_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid taps dtype");
     if (!dtype_valid(x_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid x dtype");
     if (nch < 1 || nch > 65535) MDSP_FAIL(MDSP_ERR_ARGUMENT, "nch must be in [1, 65535]");
     const int64_t g = gcd64(L, M);  // Rational normalisation (numerator / denominator of L//M)
@@ -2167,17 +2204,21 @@ int mdsp_fir_create(mdsp_fir* fo, const void* taps_host, int64_t hlen, int64_t L
     f->kind = (L == 1 && M == 1) ? 0 : (M == 1 ? 1 : (L == 1 ? 2 : 3));
     f->tp = cdiv(hlen, L);                       // taps2pfb: tapsPerPhase = ceil(hLen / Nphi)   (stream_filt.jl:296)
     f->hl = f->tp - 1;                           // historyLen (:163,:166,:169,:172)
-    f->acc_double = (taps_dtype == MDSP_F64) || dtype_is_double(x_dtype);  // promote_type(Th, Tx)
-    f->out_dtype = dtype_is_complex(x_dtype) ? (f->acc_double ? MDSP_C64 : MDSP_C32) : (f->acc_double ? MDSP_F64 : MDSP_F32);
-    // pfbT[i*L + c] = pfb[i+1, c+1] with pfb[row, col] = h[(tp-row)*L + col] (1-based rows from the bottom, :300-304)
-    const size_t np = (size_t)(f->tp * L);
+    f->ctaps = dtype_is_complex(taps_dtype);
+    f->acc_double = dtype_is_double(taps_dtype) || dtype_is_double(x_dtype);  // promote_type(Th, Tx)
+    f->out_dtype = (f->ctaps || dtype_is_complex(x_dtype)) ? (f->acc_double ? MDSP_C64 : MDSP_C32) : (f->acc_double ? MDSP_F64 : MDSP_F32);
+    // pfbT[i*L + c] = pfb[i+1, c+1] with pfb[row, col] = h[(tp-row)*L + col] (1-based rows from the bottom, :300-304); complex taps: (re, im) pairs
+    const size_t nc = f->ctaps ? 2 : 1, np = (size_t)(f->tp * L) * nc;
+    const bool taps_f32 = !dtype_is_double(taps_dtype);
     std::vector<double> pd(np, 0.0);
     for (int64_t row = 0; row < f->tp; ++row)       // row 0 = top of the matrix
         for (int64_t col = 0; col < L; ++col) {
             const int64_t hidx = (f->tp - 1 - row) * L + col;  // bottom row holds h[0..L)
-            double v = 0;
-            if (hidx < hlen) v = taps_dtype == MDSP_F32 ? (double)((const float*)taps_host)[hidx] : ((const double*)taps_host)[hidx];
-            pd[(size_t)(row * L + col)] = v;
+            if (hidx >= hlen) continue;
+            for (size_t c = 0; c < nc; ++c) {
+                const size_t src = (size_t)hidx * nc + c;
+                pd[(size_t)(row * L + col) * nc + c] = taps_f32 ? (double)((const float*)taps_host)[src] : ((const double*)taps_host)[src];
+            }
         }
     int st = MDSP_OK;
     if (f->acc_double) {
@@ -2273,7 +2314,7 @@ int mdsp_fir_info(mdsp_fir f, int* kind, int64_t* L, int64_t* M, int64_t* taps_p
 int mdsp_fir_mm_geometry(int64_t L, int64_t M, int64_t hlen, int taps_dtype, int x_dtype, int64_t* out12) {
     if (!out12) MDSP_FAIL(MDSP_ERR_ARGUMENT, "out is NULL");
     if (L < 1 || M < 1 || hlen < 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "L, M, hlen must be positive");
-    if ((taps_dtype != MDSP_F32 && taps_dtype != MDSP_F64) || !dtype_valid(x_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid dtype");
+    if (!dtype_valid(taps_dtype) || !dtype_valid(x_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid dtype");
     const int64_t g0 = gcd64(L, M);
     mdsp_fir_s f;   // no device objects are touched: pure geometry
     f.L = L / g0;
@@ -2283,7 +2324,8 @@ int mdsp_fir_mm_geometry(int64_t L, int64_t M, int64_t hlen, int taps_dtype, int
     f.hl = f.tp - 1;
     f.taps_dtype = taps_dtype;
     f.x_dtype = x_dtype;
-    f.acc_double = (taps_dtype == MDSP_F64) || dtype_is_double(x_dtype);
+    f.ctaps = dtype_is_complex(taps_dtype);   // (fits = 0: the matrix-core kernel takes real taps only)
+    f.acc_double = dtype_is_double(taps_dtype) || dtype_is_double(x_dtype);
     const FirChoiceScope choice(&f);
     const FirMGeo g = fir_mm_geo(&f);
     const int64_t v[12] = {g.ok ? 1 : 0, g.RB, g.Lr, g.Mr, g.NB, g.NG, g.steps, g.CH, g.CS, g.nd, g.ns, (int64_t)g.lds_bytes};
@@ -2301,7 +2343,8 @@ int mdsp_fir_kernel_path(mdsp_fir f, int64_t xlen, int* path) {
     a.L = (int)f->L;
     a.M = (int)f->M;
     const FirChoiceScope choice(f);
-    *path = fir_dec_geo(f).ok ? 3 : fir_mm_use(f, a) ? 2 : (fir_fast_ok(f, 2) || fir_fast_ok(f, 1) || fir_reg_use(f)) ? 1 : 0;   // 3: decimator kernel, 2: matrix cores, 1: register taps, 0: generic
+    if (f->ctaps) *path = fir_reg_use(f) ? 1 : 0;   // complex taps: 1 the complex register-tap kernel (fir_creg.hip), 0 generic
+    else *path = fir_dec_geo(f).ok ? 3 : fir_mm_use(f, a) ? 2 : (fir_fast_ok(f, 2) || fir_fast_ok(f, 1) || fir_reg_use(f)) ? 1 : 0;   // 3: decimator kernel, 2: matrix cores, 1: register taps, 0: generic
     return MDSP_OK;
 }
 
@@ -2879,7 +2922,7 @@ int mdsp_firarb_create(mdsp_firarb* fo, const void* taps_host, int64_t hlen, dou
     if (!(rate > 0.0)) MDSP_FAIL(MDSP_ERR_DOMAIN, "rate must be greater than 0");          // stream_filt.jl:151
     if (!taps_host || hlen < 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "filter taps must be non-empty");
     if (nphi < 1 || nphi > (int64_t(1) << 20)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "Nphi must be in [1, 2^20]");
-    if (taps_dtype != MDSP_F32 && taps_dtype != MDSP_F64) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "only real Float32/Float64 taps are supported on the device");
+    if (taps_dtype != MDSP_F32 && taps_dtype != MDSP_F64) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "FIRArbitrary takes real Float32/Float64 taps only (complex taps: integer and rational ratios)");
     if (!dtype_valid(x_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid x dtype");
     if (nch < 1 || nch > 65535) MDSP_FAIL(MDSP_ERR_ARGUMENT, "nch must be in [1, 65535]");
     std::unique_ptr<mdsp_firarb_s> f(new mdsp_firarb_s());
@@ -3154,6 +3197,34 @@ template <typename A> int extrapolate_run(const void* x, int64_t n, int64_t ncol
 
 extern "C" {
 
+// The promotion of a tap dtype and a signal dtype (promote_type): complex if either is, double if either is.
+static int tdfir_promote(int taps_dtype, int x_dtype) {
+    const bool dbl = dtype_is_double(taps_dtype) || dtype_is_double(x_dtype), c = dtype_is_complex(taps_dtype) || dtype_is_complex(x_dtype);
+    return c ? (dbl ? MDSP_C64 : MDSP_C32) : (dbl ? MDSP_F64 : MDSP_F32);
+}
+
+int mdsp_tdfir_state_exec_t(const void* taps_host, int64_t nb, int taps_dtype, int x_dtype, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx,
+                            void* y_dev, int64_t ldy, void* si_dev, void* stream) {
+    if (!taps_host || nb < 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "filter vector b must be non-empty");
+    if (!dtype_valid(taps_dtype) || !dtype_valid(x_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid dtype");
+    // x, y and the state are all of the promoted dtype, which the signal must already have (the state IS of the output's type, filt.jl:149-151)
+    if (tdfir_promote(taps_dtype, x_dtype) != x_dtype) MDSP_FAIL(MDSP_ERR_ARGUMENT, "x_dtype must be the promotion of the tap and signal dtypes");
+    if (!dtype_is_complex(taps_dtype)) {
+        if (taps_dtype != dtype_real_of(x_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "real taps must be in the precision of x_dtype");
+        return mdsp_tdfir_state_exec(taps_host, nb, x_dtype, x_dev, nx, ncols, ldx, y_dev, ldy, si_dev, stream);
+    }
+    if (taps_dtype != x_dtype) MDSP_FAIL(MDSP_ERR_ARGUMENT, "complex taps must be in the precision of x_dtype");
+    if (nx < 0 || ncols < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "negative size");
+    if (nb < 2) MDSP_FAIL(MDSP_ERR_ARGUMENT, "a one-tap filter has no state; scale the signal instead");
+    if (nb - 1 > 256 * 16) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "stateful time-domain FIR supports at most 4097 taps");
+    if (nx == 0 || ncols == 0) return MDSP_OK;
+    if (ncols > 65535) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "more than 65535 columns per call");
+    if (!x_dev || !y_dev || !si_dev) MDSP_FAIL(MDSP_ERR_ARGUMENT, "NULL buffer");
+    hipStream_t st = as_stream(stream);
+    if (x_dtype == MDSP_C32) return tdfir_state_run<cx<float>, cx<float>>(taps_host, nb, x_dev, nx, ncols, ldx, y_dev, ldy, si_dev, st);
+    return tdfir_state_run<cx<double>, cx<double>>(taps_host, nb, x_dev, nx, ncols, ldx, y_dev, ldy, si_dev, st);
+}
+
 int mdsp_tdfir_state_exec(const void* taps_host, int64_t nb, int dtype, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx, void* y_dev,
                           int64_t ldy, void* si_dev, void* stream) {
     if (!taps_host || nb < 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "filter vector b must be non-empty");
@@ -3207,6 +3278,29 @@ int mdsp_tdfir_exec(const void* taps_host, int64_t nb, int dtype, const void* x_
     key.append(static_cast<const char*>(taps_host), (size_t)nb * dtype_size(dtype_real_of(dtype)));
     void* h = nullptr;
     MDSP_TRY(plan_cache_get(key, &h, [&](void** out) { return mdsp_fir_create(reinterpret_cast<mdsp_fir*>(out), taps_host, nb, 1, 1, dtype_real_of(dtype), dtype, ncols); },
+                            [](void* p) { (void)mdsp_fir_destroy(static_cast<mdsp_fir>(p)); }));
+    mdsp_fir f = static_cast<mdsp_fir>(h);
+    MDSP_TRY(fir_reset_on(f, as_stream(stream), true));   // zero initial state: every call is a fresh filt(b, a, x)
+    int64_t nw = 0;
+    return mdsp_fir_exec(f, x_dev, nx, ldx, y_dev, nx, ldy, &nw, stream);
+}
+
+// The same with an explicit tap dtype (real or complex) next to the signal's: x of x_dtype, y of promote_type(taps_dtype, x_dtype).  Complex taps take the
+// plain complex product (no conjugate), oldest sample first.
+int mdsp_tdfir_exec_t(const void* taps_host, int64_t nb, int taps_dtype, int x_dtype, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx,
+                      void* y_dev, int64_t ldy, void* stream) {
+    if (!taps_host || nb < 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "filter vector b must be non-empty");
+    if (!dtype_valid(taps_dtype) || !dtype_valid(x_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid dtype");
+    if (nx < 0 || ncols < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "negative size");
+    if (nx == 0 || ncols == 0) return MDSP_OK;
+    if (ncols > 65535) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "more than 65535 columns per call");
+    std::string key = plan_cache_key('g', stream);   // (its own key class: the tap dtype is part of the key)
+    key.append(reinterpret_cast<const char*>(&taps_dtype), sizeof(taps_dtype));
+    key.append(reinterpret_cast<const char*>(&x_dtype), sizeof(x_dtype));
+    key.append(reinterpret_cast<const char*>(&ncols), sizeof(ncols));
+    key.append(static_cast<const char*>(taps_host), (size_t)nb * dtype_size(taps_dtype));
+    void* h = nullptr;
+    MDSP_TRY(plan_cache_get(key, &h, [&](void** out) { return mdsp_fir_create(reinterpret_cast<mdsp_fir*>(out), taps_host, nb, 1, 1, taps_dtype, x_dtype, ncols); },
                             [](void* p) { (void)mdsp_fir_destroy(static_cast<mdsp_fir>(p)); }));
     mdsp_fir f = static_cast<mdsp_fir>(h);
     MDSP_TRY(fir_reset_on(f, as_stream(stream), true));   // zero initial state: every call is a fresh filt(b, a, x)

@@ -59,10 +59,20 @@ def _cast_result(t, T: np.dtype):
 # tdfir plumbing shared with Filters.tdfilt
 # ---------------------------------------------------------------------------------------------------------
 def _tdfir(b: np.ndarray, x, T: np.dtype):
-    """Zero-state FIR along the first axis of x with real taps b, result eltype T."""
-    if b.dtype.kind == "c":
-        raise UnsupportedError("complex FIR taps are not accelerated (use DSP.jl on the CPU)")
+    """Zero-state FIR along the first axis of x with taps b, result eltype T.  Complex taps are multiplied as they are (no conjugate,
+    dspbase.jl:95-105); the signal keeps its own class on the device and the result is complex."""
     W = _compute_dtype(T)
+    if b.dtype.kind == "c":
+        xdt = _dev.np_dtype_of(x)
+        Wx = xdt if xdt in _FFT_TYPES else (W if xdt.kind == "c" else np.dtype(np.float32 if W == np.dtype(np.complex64) else np.float64))
+        cols, shape = _dev.to_columns(x, Wx)
+        ncols, nx = cols.shape
+        out = _dev.empty_columns(ncols, nx, W)
+        if nx and ncols:
+            taps = np.ascontiguousarray(b, dtype=W)
+            _lib.check(_lib.lib().mdsp_tdfir_exec_t(taps.ctypes.data_as(C.c_void_p), len(taps), _dev.md_dtype(W), _dev.md_dtype(Wx), _dev.ptr(cols),
+                                                    nx, ncols, nx, _dev.ptr(out), nx, _dev.stream_ptr()))
+        return _dev.from_columns(out, shape, x)
     cols, shape = _dev.to_columns(x, W)
     ncols, nx = cols.shape
     out = _dev.empty_columns(ncols, nx, W)
@@ -74,7 +84,7 @@ def _tdfir(b: np.ndarray, x, T: np.dtype):
 
 
 def filt(b, a, x):
-    """``filt(b, a, x)`` (dspbase.jl:14-66) for FIR filters (scalar / length-1 ``a``).
+    """``filt(b, a, x)`` (dspbase.jl:14-66) for FIR filters (scalar / length-1 ``a``); ``b`` and ``a`` real or complex.
 
     IIR (``length(a) > 1``) is a serial recursion per column and is out of scope for the device path.
     """

@@ -79,13 +79,29 @@ def fftfilt_(out, b, x, nfft: int | None = None):
     return _assign(out, fftfilt(b, x, nfft))
 
 
+def _cfftfilt(b: np.ndarray, x, engine: int = _lib.ENGINE_AUTO):
+    """Complex taps longer than SMALL_FILT_CUTOFF: the complex overlap-save plan in FILT mode, a real signal widened to the complex compute type."""
+    W = _compute_dtype(util.promote_type(b.dtype, _dev.np_dtype_of(x)))
+    cols, shape = _dev.to_columns(x, W)
+    ncols, nx = cols.shape
+    if nx == 0 or ncols == 0:
+        return _dev.from_columns(_dev.empty_columns(ncols, nx, W), shape, x)
+    plan = OlsPlan(b.astype(W), optimalfftfiltlength(len(b), nx), nx, _lib.OLS_FILT, engine, cached=True)
+    return _dev.from_columns(plan.exec(cols, nx), shape, x)
+
+
 def filt(b, x, engine: int = _lib.ENGINE_AUTO):
     """``filt(b, x)`` (filt.jl:445-446, :525-555): FFT overlap-save when both are real and
-    length(b) > SMALL_FILT_CUTOFF (66), time domain otherwise."""
+    length(b) > SMALL_FILT_CUTOFF (66), time domain otherwise.
+
+    Complex taps: time domain up to SMALL_FILT_CUTOFF taps, as the reference; longer ones take the complex overlap-save plan, where the
+    reference stays in the time domain (filt.jl:553) -- the results agree to rounding, and the cost does not grow with length(b)."""
     bv = _host_vec(b)
     xdt = _dev.np_dtype_of(x)
     if bv.dtype.kind in _REAL_KINDS and xdt.kind in _REAL_KINDS and len(bv) > SMALL_FILT_CUTOFF:
         return _fftfilt(bv, x, optimalfftfiltlength(len(bv), int(x.shape[0])), engine)
+    if bv.dtype.kind == "c" and len(bv) > SMALL_FILT_CUTOFF:
+        return _cfftfilt(bv, x, engine)
     return tdfilt(bv, x)
 
 
@@ -128,6 +144,10 @@ class FIRFilter:
 
     ``FIRFilter(h, rate::float, Nphi=32)`` is the arbitrary-rate resampler (FIRArbitrary, stream_filt.jl:92-156): state
     ``phi_accumulator`` (Float64), ``phi_idx``, ``alpha``, ``input_deficit``, ``x_idx``.
+
+    Complex taps (ComplexF32 stays ComplexF32, anything else complex is widened to ComplexF64) run at integer and rational ratios: a tap
+    times a sample is the plain complex product (``unsafe_dot``, util.jl:225-283: no conjugate) and the output eltype is
+    ``promote_type(eltype(h), eltype(x))``.  FIRArbitrary with complex taps raises ``UnsupportedError``.
     """
 
     KINDS = ("FIRStandard", "FIRInterpolator", "FIRDecimator", "FIRRational", "FIRArbitrary")
@@ -136,8 +156,11 @@ class FIRFilter:
         self.exact = bool(exact)     # exact=True: the generic kernel only -- every output reads exactly its own window (mdsp_fir_set_exact)
         self.h = _host_vec(h)
         if self.h.dtype.kind == "c":
-            raise UnsupportedError("complex FIR taps are not accelerated")
-        if self.h.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+            if isinstance(ratio, (float, np.floating)):
+                raise UnsupportedError("FIRArbitrary (FIRFilter(h, rate::AbstractFloat)) with complex taps is not accelerated")
+            if self.h.dtype != np.dtype(np.complex64):
+                self.h = self.h.astype(np.complex128)
+        elif self.h.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
             self.h = self.h.astype(np.float64)
         self._handle = None
         self._xdtype = None
@@ -440,11 +463,12 @@ class DF2TFilter:
             raise UnsupportedError("IIR DF2TFilter is a serial recursion; only FIR coefficients run on the device")
         if av[0] == 0:
             raise ArgumentError("filter vector a[1] must be nonzero")
-        if bv.dtype.kind == "c":
-            raise UnsupportedError("complex FIR taps are not accelerated")
         if av[0] != 1:
             bv = bv / av[0]                                             # PolynomialRatio normalises by a[1]
-        self.b = bv if bv.dtype in (np.dtype(np.float32), np.dtype(np.float64)) else bv.astype(np.float64)
+        if bv.dtype.kind == "c":                                        # complex coefficients: a complex TDF-II state (filt.jl:149-151)
+            self.b = bv if bv.dtype == np.dtype(np.complex64) else bv.astype(np.complex128)
+        else:
+            self.b = bv if bv.dtype in (np.dtype(np.float32), np.dtype(np.float64)) else bv.astype(np.float64)
         T = util.promote_type(self.b.dtype, dtype) if dtype is not None else self.b.dtype   # zeros(promote_type(T, V), ...), :150
         self._T = _compute_dtype(T)
         self.state = _dev.torch.zeros((len(self.b) - 1,) + tuple(coldims), dtype=_dev.torch_dtype(self._T), device=_dev.device())
@@ -459,23 +483,28 @@ class DF2TFilter:
         ncols, nx = cols.shape
         nb = len(self.b)
         if nb == 1:                                                     # mul!(out, x, b[1]), :163
-            return _dev.from_columns(cols * float(self.b[0]), shape, x)
+            return _dev.from_columns(cols * (complex(self.b[0]) if self.b.dtype.kind == "c" else float(self.b[0])), shape, x)
         if self._T != W:                                                # a wider signal eltype widens the state for good
             self.state = self.state.to(_dev.torch_dtype(W))
             self._T = W
         out = _dev.empty_columns(ncols, nx, W)
         if nx and ncols:
             si = self.state.reshape(nb - 1, -1).t().contiguous()        # (ncols, nb-1): one register file per column
-            taps = np.ascontiguousarray(self.b, dtype=np.float32 if W in (np.dtype(np.float32), np.dtype(np.complex64)) else np.float64)
-            _lib.check(_lib.lib().mdsp_tdfir_state_exec(taps.ctypes.data_as(C.c_void_p), nb, _dev.md_dtype(W), _dev.ptr(cols), nx, ncols, nx,
-                                                        _dev.ptr(out), nx, _dev.ptr(si), _dev.stream_ptr()))
+            if self.b.dtype.kind == "c":                                # W is complex: taps, signal and state all in it
+                taps = np.ascontiguousarray(self.b, dtype=W)
+                _lib.check(_lib.lib().mdsp_tdfir_state_exec_t(taps.ctypes.data_as(C.c_void_p), nb, _dev.md_dtype(W), _dev.md_dtype(W), _dev.ptr(cols),
+                                                              nx, ncols, nx, _dev.ptr(out), nx, _dev.ptr(si), _dev.stream_ptr()))
+            else:
+                taps = np.ascontiguousarray(self.b, dtype=np.float32 if W in (np.dtype(np.float32), np.dtype(np.complex64)) else np.float64)
+                _lib.check(_lib.lib().mdsp_tdfir_state_exec(taps.ctypes.data_as(C.c_void_p), nb, _dev.md_dtype(W), _dev.ptr(cols), nx, ncols, nx,
+                                                            _dev.ptr(out), nx, _dev.ptr(si), _dev.stream_ptr()))
             self.state = si.t().reshape(self.state.shape).contiguous()
         return _dev.from_columns(out, shape, x)
 
 
 def filtfilt(b, *args):
     """``filtfilt(b, x)`` / ``filtfilt(b, a, x)`` with scalar or length-1 ``a`` (filt.jl:301-338): zero-phase FIR
-    filtering -- odd-symmetric extension by ``length(b)-1`` samples, one pass with ``conv(b, reverse(b))``, trim."""
+    filtering -- odd-symmetric extension by ``length(b)-1`` samples, one pass with ``conv(b, reverse(b))``, trim.  ``b`` real or complex."""
     if len(args) == 2:
         a, x = args
         av = _host_vec(a)
@@ -489,16 +518,24 @@ def filtfilt(b, *args):
         bv = _host_vec(b)
     else:
         raise TypeError("filtfilt(b, x) or filtfilt(b, a, x)")
-    if bv.dtype.kind == "c":
-        raise UnsupportedError("complex FIR taps are not accelerated")
     nb = len(bv)
     n = int(x.shape[0])
     if nb - 1 > n - 1:
         raise ArgumentError("the signal must be longer than the filter order")   # sig[2 + pad_length - i] is a BoundsError in the reference
-    # newb = conv(b, reverse(b)), built as the reference builds it: causal half by filt!, mirrored (:309-314)
-    bw = bv.astype(np.float64) if bv.dtype.kind != "f" else bv
+    # newb = conv(b, reverse(b)), built as the reference builds it: causal half by filt!, mirrored (:309-314); complex b: the same sums in
+    # complex arithmetic on the host, in the taps' precision, no conjugate
+    if bv.dtype.kind == "c":
+        bw = bv if bv.dtype == np.dtype(np.complex64) else bv.astype(np.complex128)
+    else:
+        bw = bv.astype(np.float64) if bv.dtype.kind != "f" else bv
     rev = bw[::-1].copy()
-    half = np.array([np.dot(bw[:k + 1][::-1], rev[:k + 1]) for k in range(nb)], dtype=bw.dtype)
+    if bw.dtype.kind == "c":     # the TDF-II recursion of filt!(newb, b, reverse(b)) itself (dspbase.jl:95-105): innermost term first, in the taps' precision
+        xp = np.concatenate([np.zeros(nb - 1, dtype=bw.dtype), rev])
+        half = bw[nb - 1] * xp[0:nb]
+        for j in range(nb - 2, -1, -1):
+            half = xp[nb - 1 - j: 2 * nb - 1 - j] * bw[j] + half
+    else:
+        half = np.array([np.dot(bw[:k + 1][::-1], rev[:k + 1]) for k in range(nb)], dtype=bw.dtype)
     newb = np.concatenate([half, half[nb - 2::-1] if nb > 1 else half[:0]])
     xdt = _dev.np_dtype_of(x)
     W = _compute_dtype(util.promote_type(bw.dtype, xdt))

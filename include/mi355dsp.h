@@ -333,8 +333,9 @@ int mdsp_coherence_from_cs(const void* cs_dev, int64_t nch, int64_t nf, int real
  *   unsafe_dot / BLAS.dot inner products (util.jl:225-283) and shiftin! (util.jl:299-314).
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct mdsp_fir_s* mdsp_fir;
-/* taps_host: hlen taps of taps_dtype (MDSP_F32 | MDSP_F64); ratio L/M is reduced to lowest terms.
- * x_dtype: element type of the input; output type = promote(taps, x).  nch channels share the scalar state
+/* taps_host: hlen taps of taps_dtype (MDSP_F32 | MDSP_F64 | MDSP_C32 | MDSP_C64; complex taps as interleaved (re, im) pairs, multiplied
+ * as they are: no conjugate); ratio L/M is reduced to lowest terms.
+ * x_dtype: element type of the input; output type = promote(taps, x) -- complex when either is, double when either is.  nch channels share the scalar state
  * (phi_idx, input_deficit) and keep separate histories, as resample(...; dims) does per slice (:768-774). */
 int mdsp_fir_create(mdsp_fir* f, const void* taps_host, int64_t hlen, int64_t L, int64_t M, int taps_dtype,
                     int x_dtype, int64_t nch);
@@ -354,11 +355,12 @@ int mdsp_fir_info(mdsp_fir f, int* kind /*0 std,1 interp,2 decim,3 rational*/, i
 /* Which kernel mdsp_fir_exec would run for a chunk of `xlen` samples in the filter's current state: 0 generic polyphase kernel
  * (any dtype), 1 register-tap kernel (Float32 <= 64 taps per phase; Float64 / ComplexF32 / ComplexF64 <= 112, L <= 1024), 2 matrix-core kernel (rows of 16 outputs on
  * v_mfma_f32_16x16x4_f32 / v_mfma_f64_16x16x4_f64; Float32 results bit-identical to 0 / 1), 3 decimator kernel (L = 1, M <= 64, any length: a lane
- * per input phase; sums phases first, so it agrees with 0 to rounding, and reads exactly the reference's windows).  Diagnostics / tests. */
+ * per input phase; sums phases first, so it agrees with 0 to rounding, and reads exactly the reference's windows).  Complex taps: 1 the complex
+ * register-tap kernel (Float32 arithmetic <= 112 taps per phase, Float64 <= 56, L <= 1024), 0 the generic kernel; never 2 or 3.  Diagnostics / tests. */
 int mdsp_fir_kernel_path(mdsp_fir f, int64_t xlen, int* path);
 /* Geometry the matrix-core kernel would use for a filter of hlen taps at ratio L // M (pure host arithmetic, no device):
  * out12 = {fits, rounds per row RB, outputs per row Lr = RB L, samples per row Mr = RB M, column blocks NB, row groups NG, k-steps of four taps (in registers up to 64, Float64 32; beyond that fetched per tile),
- * 16-row chunks per wave CH, parts per sample CS, DMA waves, store waves, LDS bytes}.  Diagnostics / tests. */
+ * 16-row chunks per wave CH, parts per sample CS, DMA waves, store waves, LDS bytes}.  fits = 0 for complex taps.  Diagnostics / tests. */
 int mdsp_fir_mm_geometry(int64_t L, int64_t M, int64_t hlen, int taps_dtype, int x_dtype, int64_t* out12);
 /* state is exactly the reference's: 1-based phi_idx and input_deficit, history (history_len, nch) of x_dtype */
 int mdsp_fir_get_state(mdsp_fir f, int64_t* phi_idx, int64_t* input_deficit, void* history_host);
@@ -382,6 +384,7 @@ int mdsp_fir_exec_host(mdsp_fir f, const void* x_host, int64_t xlen, int64_t ldx
  *   samples written and the state after every chunk are bit-exact; the dot products run on the device.
  * ---------------------------------------------------------------------------------------------------- */
 typedef struct mdsp_firarb_s* mdsp_firarb;
+/* taps_dtype: MDSP_F32 | MDSP_F64 (complex taps: MDSP_ERR_UNSUPPORTED -- they run at integer and rational ratios, mdsp_fir_create) */
 int mdsp_firarb_create(mdsp_firarb* f, const void* taps_host, int64_t hlen, double rate, int64_t nphi, int taps_dtype,
                        int x_dtype, int64_t nch);
 int mdsp_firarb_destroy(mdsp_firarb f);
@@ -441,12 +444,21 @@ int mdsp_convnd_direct(const void* u_dev, const int64_t* su, const void* v_dev, 
  * ---------------------------------------------------------------------------------------------------- */
 int mdsp_tdfir_exec(const void* taps_host, int64_t nb, int dtype, const void* x_dev, int64_t nx, int64_t ncols,
                     int64_t ldx, void* y_dev, int64_t ldy, void* stream);
+/* The same with an explicit tap dtype: taps_host holds nb taps of taps_dtype (any of the four; complex taps are multiplied as they are, no
+ *   conjugate), x_dev is (nx, ncols) of x_dtype and y_dev of promote(taps_dtype, x_dtype). */
+int mdsp_tdfir_exec_t(const void* taps_host, int64_t nb, int taps_dtype, int x_dtype, const void* x_dev, int64_t nx,
+                      int64_t ncols, int64_t ldx, void* y_dev, int64_t ldy, void* stream);
 
 /* Stateful time-domain FIR: filt!(out, f::DF2TFilter{<:PolynomialRatio}, x) with FIR coefficients (Filters/filt.jl:153-181)
  *   advancing the TDF-II state exactly as _filt_fir!(out, b, x, si, col) does (dspbase.jl:95-105).
  *   si_dev: (nb-1, ncols) of `dtype`, read as the initial state and overwritten with the final one. */
 int mdsp_tdfir_state_exec(const void* taps_host, int64_t nb, int dtype, const void* x_dev, int64_t nx, int64_t ncols,
                           int64_t ldx, void* y_dev, int64_t ldy, void* si_dev, void* stream);
+/* The same with an explicit tap dtype, so that complex coefficients carry a complex TDF-II state (zeros(promote_type(T, V), ...),
+ *   Filters/filt.jl:149-151).  The state is of the promoted type and the signal enters the recursion in it, so x_dev, y_dev and si_dev are all of
+ *   x_dtype, which must equal promote(taps_dtype, x_dtype) (the caller widens a narrower signal); the taps are in x_dtype's precision, real or complex. */
+int mdsp_tdfir_state_exec_t(const void* taps_host, int64_t nb, int taps_dtype, int x_dtype, const void* x_dev, int64_t nx,
+                            int64_t ncols, int64_t ldx, void* y_dev, int64_t ldy, void* si_dev, void* stream);
 /* extrapolate_signal! (Filters/filt.jl:243-257), the odd-symmetric extension filtfilt applies per column:
  *   out (n + 2 pad, ncols) = [2 x[1] .- x[pad+1:-1:2]; x; 2 x[end] .- x[end-1:-1:end-pad]] */
 int mdsp_extrapolate(const void* x_dev, int64_t n, int64_t ncols, int64_t ldx, int dtype, int64_t pad, void* out_dev,

@@ -306,6 +306,16 @@ function filt(b::AbstractVector, a::Number, x::Union{AbstractArray{T},DeviceArra
     isempty(b) && throw(ArgumentError("filter vector b must be non-empty"))
     a == 0 && throw(ArgumentError("filter vector a[1] must be nonzero"))
     W = fftintype(promote_type(eltype(b), typeof(a), T))
+    if promote_type(eltype(b), typeof(a)) <: Complex       # complex taps (plain product, no conjugate): explicit tap dtype, the signal keeps its class
+        Tx = T <: Complex ? W : real(W)
+        ctaps = convert(Vector{W}, a == 1 ? b : b ./ a)
+        xc = todevice(x, Tx)
+        yc = DeviceArray{W}(size(xc))
+        n = size(xc, 1)
+        GC.@preserve ctaps check(ccall((:mdsp_tdfir_exec_t, lib), Cint, (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+                                       pointer(ctaps), length(ctaps), mdtype(W), mdtype(Tx), xc.ptr, n, ncolumns(xc), n, yc.ptr, n, C_NULL))
+        return back(yc, x)
+    end
     taps = convert(Vector{real(W)}, a == 1 ? b : b ./ a)
     xd = todevice(x, W)
     y = DeviceArray{W}(size(xd))
@@ -793,7 +803,8 @@ mutable struct FIRFilter                                                        
     nch::Int
 end
 # exact=true: the generic kernel only -- every output reads exactly its own tapsPerϕ-sample window, so NaN / Inf samples leave exactly DSP.jl's hole
-function FIRFilter(taps::Vector{Th}, ratio::Union{Integer,Rational}=1; xtype::DataType=Th, nch::Integer=1, exact::Bool=false) where {Th<:Union{Float32,Float64}}
+# complex taps (ComplexF32 / ComplexF64) are multiplied as they are, no conjugate; the output is promote_type(Th, xtype)
+function FIRFilter(taps::Vector{Th}, ratio::Union{Integer,Rational}=1; xtype::DataType=Th, nch::Integer=1, exact::Bool=false) where {Th<:Union{Float32,Float64,ComplexF32,ComplexF64}}
     p = Ref{Ptr{Cvoid}}(C_NULL)
     r = convert(Rational{Int}, ratio)
     GC.@preserve taps check(ccall((:mdsp_fir_create, lib), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cvoid}, Int64, Int64, Int64, Cint, Cint, Int64),
@@ -1042,6 +1053,30 @@ function filt(f::DF2TFilter{T}, x::AbstractVecOrMat{Tx}) where {T,Tx<:Real}
     GC.@preserve taps (nx > 0 && check(ccall((:mdsp_tdfir_state_exec, lib), Cint,
         (Ptr{Cvoid}, Int64, Cint, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
         pointer(taps), nb, mdtype(W), xd.ptr, nx, ncolumns(xd), nx, y.ptr, nx, si.ptr, C_NULL)))
+    f.state = convert(Matrix{T}, download(si))
+    download(y)
+end
+# complex coefficients: the TDF-II state is complex (zeros(promote_type(T, V), ...), filt.jl:149-151) and the signal enters the recursion widened to it
+function DF2TFilter(b::AbstractVector{<:Complex}, a::Number=1.0; coldims::Integer=1)
+    isempty(b) && throw(ArgumentError("filter coefficients must be non-empty"))
+    a == 0 && throw(ArgumentError("filter vector a[1] must be nonzero"))
+    T = eltype(b) == ComplexF32 ? ComplexF32 : ComplexF64
+    taps = convert(Vector{T}, a == 1 ? b : b ./ a)
+    DF2TFilter{T}(taps, zeros(T, length(taps) - 1, coldims))
+end
+function filt(f::DF2TFilter{T}, x::AbstractVecOrMat{Tx}) where {T<:Complex,Tx<:Number}
+    size(x, 2) == size(f.state, 2) || throw(ArgumentError("state size must match x"))
+    W = promote_type(T, fftintype(Tx))
+    nb = length(f.b)
+    nb == 1 && return convert(Array{W}, x) .* f.b[1]
+    xd = todevice(x, W)
+    nx = size(xd, 1)
+    y = DeviceArray{W}(size(xd))
+    si = upload(convert(Matrix{W}, f.state))
+    taps = convert(Vector{W}, f.b)
+    GC.@preserve taps (nx > 0 && check(ccall((:mdsp_tdfir_state_exec_t, lib), Cint,
+        (Ptr{Cvoid}, Int64, Cint, Cint, Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+        pointer(taps), nb, mdtype(W), mdtype(W), xd.ptr, nx, ncolumns(xd), nx, y.ptr, nx, si.ptr, C_NULL)))
     f.state = convert(Matrix{T}, download(si))
     download(y)
 end
