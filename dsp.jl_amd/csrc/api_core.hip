@@ -120,7 +120,6 @@ static const KnobDef kKnobs[] = {
     {"MDSP_OLS_PRIO", &Tunables::ols_prio, 1, 0, 3},
     {"MDSP_SPEC_PRIO", &Tunables::spec_prio, 1, 0, 3},
     {"MDSP_WELCH_VARIANT", &Tunables::welch_variant, 0, -1 << 20, 1 << 20},
-    {"MDSP_STFT_VARIANT", &Tunables::stft_variant, 1, -1 << 20, 1 << 20},
     {"MDSP_FIR_LDS_KIB", &Tunables::fir_lds_kib, 20, 4, 150},
     {"MDSP_ARB_NCH", &Tunables::arb_nch, 4, -1 << 20, 1 << 20},
     {"MDSP_ARB_PRIO", &Tunables::arb_prio, 0, 0, 3},

@@ -128,7 +128,9 @@ struct Tunables {
                                         //                            priority (default 1: Welch 1.374 -> 1.356 ms; STFT loads no effect, stores +5 % time)
     int ols_prio = 1;                   // MDSP_OLS_PRIO            : overlap-save kernel: bit 0 loads, bit 1 stores issued at raised wave priority (default 1:
                                         //                            1.799 -> 1.774 ms per 2^30 samples, profiles/r03l_tune_prio.json)
-    int ols_variant = 0, welch_variant = 0, stft_variant = 1;   // MDSP_{OLS,WELCH,STFT}_VARIANT : alternative kernel instantiations
+    int ols_variant = 0;                // MDSP_OLS_VARIANT         : kernel form of the PARTITIONED overlap-save plans only, 0-8 (ols.hip launch_upols_np)
+    int welch_variant = 0;              // MDSP_WELCH_VARIANT       : Welch kernel of the real Float32 nfft-4096 half-frame shape: 18, 30, 43 or 44 (spectral.hip
+                                        //                            welch_launch_n); any other number: the default rule
     int rocfft_chunk_mib = 192;         // MDSP_ROCFFT_CHUNK_MIB    : intermediates per rocFFT-engine chunk
     int fir_lds_kib = 20;               // MDSP_FIR_LDS_KIB         : staging tile of the fast polyphase kernel
     int arb_prio = 0;                   // MDSP_ARB_PRIO            : FIRArbitrary: the prologue of a workgroup at raised wave priority

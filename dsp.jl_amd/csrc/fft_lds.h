@@ -87,7 +87,7 @@ typedef float f2v __attribute__((ext_vector_type(2)));
 // MDSP_PK_NATIVE: the forms the compiler can express itself (plain add / subtract / multiply / FMA, broadcasts and swaps of a multiplicand --
 // it folds those into op_sel, and a whole-operand negation into neg_lo + neg_hi) are written on float2 vectors instead of asm.  What that buys:
 // hipcc pads every asm statement whose result the NEXT instruction reads with an `s_nop 0` (the gfx940+ dst_sel-forwarding hazard: the asm
-// might have written half a register), 240 of the 1994 instructions of welch_w64_kernel's unit loop; its own v_pk_* need no pad, and it knows
+// might have written half a register), 240 of the 1994 instructions of the unit loop of a one-wavefront Welch kernel written in HIP (since deleted); its own v_pk_* need no pad, and it knows
 // their latency when it schedules.  The forms with a per-half negation (a +- i b, the second step of a complex product) stay asm: the
 // compiler spends a v_xor + v_mov on those.
 #ifndef MDSP_PK_NATIVE
@@ -414,75 +414,6 @@ template <int N_, int E_> struct Cfg {
     static constexpr int NTWLDS = P <= 1 ? 1 : ldsoff(P - 1) + ldstw(P - 1);
 };
 
-// ------------------------------------------------------------------------------------------------ lane permutations
-// Which butterfly a thread computes in a pass is free as long as reads and writes agree: thread t runs butterflies
-// j = perm_p(t) + T*b of pass p, where perm_p permutes the low six bits of t (inside the wavefront, so global
-// accesses stay coalesced).  tools/lds_perm_search.py picks, per geometry, the bit permutations (and padding) that
-// minimise LDS bank conflicts under the MI355X banking rules (ds_write_b64: 16-lane groups / 32 banks; ds_read_b64:
-// 32-lane groups / 64 banks): N = 4096, E = 16 becomes conflict-free with one element of padding per 32
-// (192 array cycles per transform and wave instead of 256), N = 2048, E = 8 drops from 224 to 160.
-// Measured on MI355X (profiles/r01e_tune_lanes.json): the permuted schedules lose to identity lanes + the same padding,
-// because the permuted pass-0 ownership also permutes the lanes of the global loads / stores (same cache lines per
-// wave, but no longer ascending by lane) -- that costs more than the saved LDS cycles.  They stay available as tuning
-// variants (PERMUTE template flags); the defaults use identity lanes with pad shift 5.
-// The first and the last pass share their permutation so a transform's input and output ownership coincide:
-// thread t holds X[io_lane(t) + T*e] before the first and after the last pass.
-template <int N, int E> struct LanePerm {
-    static constexpr bool any = false;
-    static constexpr int src(int, int bit) { return bit; }
-    static constexpr int padshift = 4;
-};
-template <> struct LanePerm<2048, 8> {   // radices 8 8 8 4
-    static constexpr bool any = true;
-    static constexpr int src(int pass, int bit) {
-        constexpr int A[6] = {0, 4, 1, 2, 3, 5}, B[6] = {0, 1, 2, 4, 5, 3};
-        return (pass == 0 || pass == 3) ? A[bit] : (pass == 1 ? B[bit] : bit);
-    }
-    static constexpr int padshift = 5;
-};
-template <> struct LanePerm<4096, 16> {  // radices 16 16 16
-    static constexpr bool any = true;
-    static constexpr int src(int pass, int bit) {
-        constexpr int A[6] = {4, 0, 1, 2, 3, 5};
-        return (pass == 0 || pass == 2) ? A[bit] : bit;
-    }
-    static constexpr int padshift = 5;
-};
-// PERMUTE = 0 reproduces the identity mapping (kernels that were not re-tuned, and the host emulation's baseline), 1 the
-// bank-conflict permutations above.
-//
-// PERMUTE = 2, "wave-private last exchange" (N = 4096, E = 16, T = 256, radices 16 16 16): passes 1 and 2 run butterfly
-// j = nibble_swap(t) = (t mod 16) * 16 + t div 16.  With that ownership the 16 operands of a pass-2 butterfly are produced by the 16
-// lanes of ONE 16-lane row of one wavefront (writer lane l, output r  ->  reader lane (l div 16) * 16 + r, operand l mod 16: a 16 x 16
-// transpose inside each row), so the second exchange needs no s_barrier at all -- a wave's DS operations execute in order -- and only the
-// first exchange (all-to-all between the four waves) keeps its barrier.  Input ownership stays t + T*e (coalesced loads); the OUTPUT
-// ownership becomes nibble_swap(t) + T*e, which is why this mode is used where outputs are reduced, not stored (Welch).
-template <typename C> constexpr bool wave_private_ok() { return C::N == 4096 && C::E == 16 && C::P == 3; }
-template <typename C, int PASS, int PERMUTE> MDSP_HD int lane_perm(int t) {
-    using LP = LanePerm<C::N, C::E>;
-    if constexpr (PERMUTE == 2) {
-        static_assert(wave_private_ok<C>(), "wave-private exchange is wired for N = 4096, E = 16");
-        if constexpr (PASS == 0) return t;
-        else return ((t & 15) << 4) | ((t >> 4) & 15);
-    } else if constexpr (!PERMUTE || !LP::any || C::T < 64) return t;
-    else {
-        int out = t & ~63;
-#pragma unroll
-        for (int d = 0; d < 6; ++d) out |= ((t >> LP::src(PASS, d)) & 1) << d;
-        return out;
-    }
-}
-template <typename C, int PERMUTE> MDSP_HD int io_lane(int t) {
-    static_assert(PERMUTE != 1 || !LanePerm<C::N, C::E>::any || LanePerm<C::N, C::E>::src(0, 0) == LanePerm<C::N, C::E>::src(C::P - 1, 0),
-                  "first and last pass must share their lane permutation");
-    return lane_perm<C, 0, PERMUTE>(t);
-}
-// ownership AFTER the last pass: thread t holds X[out_lane(t) + T*e]  (== io_lane(t) except in the wave-private mode)
-template <typename C, int PERMUTE> MDSP_HD int out_lane(int t) { return lane_perm<C, C::P - 1, PERMUTE>(t); }
-// wave-private exchange: element (row-local lane a, slot b) of wavefront w, 16-lane row q lives at  w*4*272 + q*272 + a*17 + b
-// (17 = one element of padding per 16: ds_write_b64 from 16 contiguous lanes and ds_read_b64 from 32 are both conflict-free)
-MDSP_HD int wave_private_base(int t_raw) { return (t_raw >> 6) * (4 * 272) + ((t_raw >> 4) & 3) * 272; }
-
 // twiddle sources
 enum { TW_GLOBAL = 0, TW_REG = 1, TW_LDS = 2, TW_HYB = 3 };
 // TW_HYB: passes whose twiddles depend on few distinct k (Ns <= HYB_NS_MAX: a (radix-1) x Ns table of <= 2 KiB) read
@@ -539,28 +470,26 @@ template <typename C, int PASS> MDSP_HD int tw_index(int t, int b, int r) {
 }
 
 // Fill the per-thread twiddle registers (loop-invariant for a persistent workgroup).
-template <typename C, typename R, int PASS = 1, int TWMODE = TW_REG, int PERMUTE = false>
+template <typename C, typename R, int PASS = 1, int TWMODE = TW_REG>
 MDSP_HD void load_twiddles(cx<R> (&tw)[C::NTW > 0 ? C::NTW : 1], int t, const cx<R>* table) {
     if constexpr (PASS < C::P) {
         if constexpr (tw_pass_in_regs<C, TWMODE, PASS>()) {
             constexpr int Rdx = C::radix(PASS), NB = C::E / Rdx;
-            const int tp = lane_perm<C, PASS, PERMUTE>(t);
 #pragma unroll
             for (int b = 0; b < NB; ++b)
 #pragma unroll
-                for (int r = 1; r < Rdx; ++r) tw[C::twoff(PASS) + b * (Rdx - 1) + (r - 1)] = table[tw_index<C, PASS>(tp, b, r)];
+                for (int r = 1; r < Rdx; ++r) tw[C::twoff(PASS) + b * (Rdx - 1) + (r - 1)] = table[tw_index<C, PASS>(t, b, r)];
         }
-        load_twiddles<C, R, PASS + 1, TWMODE, PERMUTE>(tw, t, table);
+        load_twiddles<C, R, PASS + 1, TWMODE>(tw, t, table);
     }
 }
 
 // One Stockham pass on the thread's registers.  Non-final passes scatter their results to `lds`
 // (this transform's region); the final pass leaves X[t + T*e] in x[e].
-template <typename C, int DIR, int PASS, int TWMODE, int PADSHIFT, int PERMUTE = false, typename R>
-MDSP_HD void pass_compute(cx<R> (&x)[C::E], int t_raw, const cx<R> (&tw)[C::NTW > 0 ? C::NTW : 1], const cx<R>* table, cx<R>* lds) {
+template <typename C, int DIR, int PASS, int TWMODE, int PADSHIFT, typename R>
+MDSP_HD void pass_compute(cx<R> (&x)[C::E], int t, const cx<R> (&tw)[C::NTW > 0 ? C::NTW : 1], const cx<R>* table, cx<R>* lds) {
     constexpr int Rdx = C::radix(PASS), NB = C::E / Rdx, Ns = C::ns(PASS);
     constexpr bool LAST = PASS == C::P - 1;
-    const int t = lane_perm<C, PASS, PERMUTE>(t_raw);   // the butterflies this thread owns in this pass
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         cx<R> v[Rdx];
@@ -587,10 +516,6 @@ MDSP_HD void pass_compute(cx<R> (&x)[C::E], int t_raw, const cx<R> (&tw)[C::NTW 
         if constexpr (LAST) {
 #pragma unroll
             for (int r = 0; r < Rdx; ++r) x[b + r * NB] = v[r];
-        } else if constexpr (PERMUTE == 2 && PASS == C::P - 2) {   // wave-private transpose: writer (lane a of its row, output r) -> slot a*17 + r
-            const int base = wave_private_base(t_raw) + (t_raw & 15) * 17;
-#pragma unroll
-            for (int r = 0; r < Rdx; ++r) lds[base + r] = v[r];
         } else {
             const int j = t + C::T * b;
             const int base = lds_pad<PADSHIFT>((j / Ns) * (Ns * Rdx) + (j & (Ns - 1)));
@@ -601,7 +526,7 @@ MDSP_HD void pass_compute(cx<R> (&x)[C::E], int t_raw, const cx<R> (&tw)[C::NTW 
 }
 
 // Pass 0 of a forward E = 16 transform whose input is q[e] w[e] (e < 8), f[e] w[e + 8]: the window rides in the butterfly's first stage
-// (bfly16_win); results are scattered exactly as pass_compute<.., PASS = 0> does.  Identity lanes only.
+// (bfly16_win); results are scattered exactly as pass_compute<.., PASS = 0> does.
 template <typename C, int PADSHIFT, typename R> MDSP_HD void pass0_scatter(const cx<R> (&v)[16], int t, cx<R>* lds) {
     const int base = lds_pad<PADSHIFT>(t * 16);
 #pragma unroll
@@ -616,13 +541,8 @@ MDSP_HD void pass0_windowed(const cx<R> (&q)[8], const cx<R> (&f)[8], const cx<R
 }
 
 // After the barrier that follows a non-final pass: fetch the operands of the next pass.
-template <typename C, int PADSHIFT, int NEXT = 1, int PERMUTE = false, typename R> MDSP_HD void pass_reload(cx<R> (&x)[C::E], int t_raw, const cx<R>* lds) {
-    const int t = lane_perm<C, NEXT, PERMUTE>(t_raw);   // operands of the pass that follows
-    if constexpr (PERMUTE == 2 && NEXT == C::P - 1) {   // wave-private transpose: reader lane c of its row takes operand e from slot e*17 + c
-        const int base = wave_private_base(t_raw) + (t_raw & 15);
-#pragma unroll
-        for (int e = 0; e < C::E; ++e) x[e] = lds[base + 17 * e];
-    } else if constexpr (PADSHIFT >= 31 || C::T % (1 << (PADSHIFT >= 31 ? 0 : PADSHIFT)) == 0) {
+template <typename C, int PADSHIFT, typename R> MDSP_HD void pass_reload(cx<R> (&x)[C::E], int t, const cx<R>* lds) {
+    if constexpr (PADSHIFT >= 31 || C::T % (1 << (PADSHIFT >= 31 ? 0 : PADSHIFT)) == 0) {
         const int base = lds_pad<PADSHIFT>(t);
 #pragma unroll
         for (int e = 0; e < C::E; ++e) x[e] = lds[base + lds_padc<PADSHIFT>(C::T * e)];

@@ -189,109 +189,27 @@ __device__ __forceinline__ void ols_store(const cx<R> (&v)[E], const OlsFusedArg
     }
 }
 
-// Staged store of a unit of REAL Float32 blocks ("a store path decoupled from ..."): after the inverse transform a thread holds
-// outputs i = t + T e -- one 4-byte store per lane, 256 contiguous bytes per wave instruction, at an odd element offset (L = nfft - nb + 1).
-// With the transform removed those stores alone take 1.89 ms per 2^30 samples (2.3 TB/s) against 0.82 ms for the loads and 5.2 TB/s for a float4
-// write stream (profiles/r02o_ablation.json): the store PATTERN, not HBM, bounded the kernel.  Here the unit's 2 L valid outputs -- which are
-// CONTIGUOUS in y: block a then block b -- go through the (now idle) exchange buffer: ds_write_b32 in thread order, one barrier, ds_read_b128,
-// and every lane stores 16 bytes: 1 KiB contiguous per wave instruction.  Only units that lie wholly inside the output take this path.
-template <typename R, int E, int T, int N>
-__device__ __forceinline__ void ols_store_staged(const cx<R> (&v)[E], const OlsFusedArgs& a, OlsPos q, int t, float* S) {
-    static_assert(sizeof(R) == 4, "staged stores are wired for Float32");
-    typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const int lead = a.nb - 1, L = (int)a.L, twoL = 2 * L;
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int j = t + T * e - lead;
-        if (j >= 0) {
-            S[j] = v[e].x;
-            S[L + j] = v[e].y;
-        }
-    }
-    fft::wg_sync<T>();
-    constexpr int NV = (2 * N + 4 * T - 1) / (4 * T);   // float4 vectors per thread (2 L <= 2 N floats)
-    f4 r[NV];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-        const int idx = 4 * (t + T * c);
-        r[c] = idx + 4 <= ((twoL + 3) & ~3) ? *reinterpret_cast<const f4*>(S + idx) : f4{0.f, 0.f, 0.f, 0.f};   // S is 16-byte aligned, idx a multiple of 4
-    }
-    fft::wg_sync<T>();   // the buffer is the next unit's first exchange
-    const int64_t off0 = 2 * q.p * a.L;
-    float* yc = static_cast<float*>(a.y) + q.col * a.ldy + off0;
-    const __amdgpu_buffer_rsrc_t w = io::make_rsrc(yc, (int64_t)twoL * 4);
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-        const int idx = 4 * (t + T * c);
-        if (idx + 4 <= twoL) {
-            u4 d;
-            d.x = __float_as_uint(r[c].x); d.y = __float_as_uint(r[c].y); d.z = __float_as_uint(r[c].z); d.w = __float_as_uint(r[c].w);
-            __builtin_amdgcn_raw_buffer_store_b128(d, w, idx * 4, 0, MDSP_IO_AUX_STORE);
-        } else if (idx < twoL) {   // the one vector that straddles the end of the unit (2 L is not a multiple of 4)
-            io::Ld<float>::store(r[c].x, w, idx * 4);
-            if (idx + 1 < twoL) io::Ld<float>::store(r[c].y, w, idx * 4 + 4);
-            if (idx + 2 < twoL) io::Ld<float>::store(r[c].z, w, idx * 4 + 8);
-        }
-    }
-}
-
-// ---- LDS-DMA staging of the NEXT unit's samples (round 3) ----------------------------------------------------------------------------
-// Without a prefetch a unit's wave parks ~2 us on its loads at the top of every iteration, and with four two-wave workgroups per CU only
-// ~25 KiB per CU are outstanding on average: the read side of the kernel is capped by bytes in flight (bandwidth = outstanding / latency),
-// not by HBM.  A register prefetch costs the VGPRs that pay for the fourth workgroup (round 2 measured it slower).  buffer_load ... lds costs
-// none: the contiguous span of the next unit -- its two real blocks overlap by nb - 1 samples, so it is ONE run of L + N samples -- goes from
-// HBM straight into a 2 N-sample LDS buffer while this unit is transformed, and the next iteration starts with ds_reads instead of a trip to
-// memory.  Hand-issued (the compiler would make every later ds_read wait for a DMA it knows about); M0 holds the LDS address and is saved
-// and restored inside the statement.
-using io::dma_i4;
-using io::dma_rsrc;
-using io::dma256;
-using io::dma64;
-// A unit whose L + N samples lie wholly inside the column (both blocks exist, no zero padding in front or behind) is staged; the handful of
-// edge units of a column keep the direct loads (hardware zero fill).
-__device__ __forceinline__ bool ols_unit_interior(const OlsFusedArgs& a, OlsPos q, int N) {
-    const int64_t g0 = 2 * q.p, start = g0 * a.L - (a.nb - 1);
-    return q.live && (g0 + 1) < a.nblocks && start >= 0 && start + a.L + N <= a.nx;
-}
-// issue the DMA of unit q's span into `stage` (T threads = T / 64 waves share the granules)
-template <int T> __device__ __forceinline__ void ols_dma_issue(const OlsFusedArgs& a, OlsPos q, int N, float* stage, int tid) {
-    const float* xc = static_cast<const float*>(a.x) + q.col * a.ldx;
-    const int64_t start = 2 * q.p * a.L - (a.nb - 1);
-    const int span = (int)a.L + N;                                  // floats
-    const dma_i4 r = dma_rsrc(xc + start, (long long)span * 4);
-    const unsigned base = io::lds_byte_address(stage);
-    const int wave = __builtin_amdgcn_readfirstlane(tid / 64), lane = tid & 63;
-    constexpr int NW = T / 64;
-    const int nfull = span / 256;
-    for (int g = wave; g < nfull; g += NW) dma256(r, base + (unsigned)g * 1024u, g * 1024 + lane * 16);
-    const int ntail = (span - nfull * 256 + 63) / 64;               // 64-dword granules behind the last full one
-    for (int g = wave; g < ntail; g += NW) dma64(r, base + (unsigned)nfull * 1024u + (unsigned)g * 256u, nfull * 1024 + g * 256 + lane * 4);
-}
-
-template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, bool CPLX, int MINW, int NBUF, bool PREFETCH, bool HREG = true, int PERM = false, bool STAGE = false, bool XDMA = false,
-          bool ROWS = false>
-__global__ __launch_bounds__((N / E) * G, MINW) void ols_fused_kernel(OlsFusedArgs a) {
-    static_assert(!ROWS || (CPLX && !HREG && !PERM), "the rows form: complex blocks, one spectrum row per block");
+template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false>
+__global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs a) {
+    static_assert(!ROWS || (CPLX && !HREG), "the rows form: complex blocks, one spectrum row per block");
     using C = fft::Cfg<N, E>;
-    constexpr int T = C::T;
+    constexpr int T = C::T, PADSHIFT = 4;
     static_assert(T % 64 == 0, "a transform must own whole wavefronts (uniform descriptors)");
     constexpr int NTWA = C::NTW > 0 ? C::NTW : 1;
     constexpr int REGION = fft::wg_lds_elems<C, PADSHIFT, NBUF>();
     __shared__ __attribute__((aligned(16))) cx<R> lds_all[G * REGION];
-    const int t = threadIdx.x % T;
-    const int ti = fft::io_lane<C, PERM>(t);   // this thread owns elements ti + T*e of a unit (ti == t unless lane-permuted)
+    const int t = threadIdx.x % T;   // this thread owns elements t + T*e of a unit
     const int slot = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / T));  // wave-uniform by construction (T % 64 == 0)
     cx<R>* lds = lds_all + slot * REGION;
     const cx<R>* table = static_cast<const cx<R>*>(a.table);
 
     cx<R> tw[NTWA];
     __shared__ __attribute__((aligned(16))) cx<R> twl[(TWMODE == fft::TW_LDS || TWMODE == fft::TW_HYB) ? fft::tw_lds_entries<C, TWMODE>() : 1];
-    const cx<R>* twsrc = fft::wg_twiddle_setup<C, TWMODE, PERM>(tw, twl, t, slot, table);
+    const cx<R>* twsrc = fft::wg_twiddle_setup<C, TWMODE>(tw, twl, t, slot, table);
     cx<R> Hr[HREG ? E : 1];
     if constexpr (HREG) {
 #pragma unroll
-        for (int e = 0; e < E; ++e) Hr[e] = static_cast<const cx<R>*>(a.H)[ti + T * e];
+        for (int e = 0; e < E; ++e) Hr[e] = static_cast<const cx<R>*>(a.H)[t + T * e];
     }
     const __amdgpu_buffer_rsrc_t hrsrc = io::make_rsrc(a.H, (int64_t)N * (int64_t)sizeof(cx<R>));
 
@@ -299,34 +217,14 @@ __global__ __launch_bounds__((N / E) * G, MINW) void ols_fused_kernel(OlsFusedAr
     OlsWalk walk{a.u_begin + ((int64_t)blockIdx.x * G + slot) * a.run_len, 0};
     OlsPos cur = ols_pos(a, walk, a.niter > 0);
     OlsRaw<R, E, CPLX> raw;
-    constexpr bool DMA = XDMA && !CPLX && sizeof(R) == 4 && G == 1 && !PERM && !PREFETCH && C::P > 1;
-    __shared__ __attribute__((aligned(16))) float stage[DMA ? 2 * N : 4];   // the staged span: L + N <= 2 N samples
-    [[maybe_unused]] bool cur_staged = false;
-    if constexpr (DMA) {
-        cur_staged = ols_unit_interior(a, cur, N);                           // wave-uniform
-        if (cur_staged) ols_dma_issue<T>(a, cur, N, stage, threadIdx.x);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    if constexpr (PREFETCH) ols_issue_loads<R, E, T, CPLX>(raw, a, cur, ti);
+    if constexpr (PREFETCH) ols_issue_loads<R, E, T, CPLX>(raw, a, cur, t);
     for (int64_t it = 0; it < a.niter; ++it) {   // same trip count for every slot (barriers inside)
         ols_walk_next(walk, a.run_len, nslots);
         const OlsPos nxt = ols_pos(a, walk, it + 1 < a.niter);
-        if constexpr (DMA) {
-            // every wave waited for its share of this unit's DMA before it left the previous iteration (or the prologue): after the barrier
-            // the whole span is in `stage`
-            fft::wg_sync<T>();
-            if (cur_staged) {
-                const int L = (int)a.L;
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    raw.a[e] = stage[ti + T * e];
-                    raw.b[e] = stage[L + ti + T * e];
-                }
-            } else if (!MDSP_ABLATED(a, 1)) ols_issue_loads<R, E, T, CPLX>(raw, a, cur, ti);
-        } else if constexpr (!PREFETCH) {
+        if constexpr (!PREFETCH) {
             if (!MDSP_ABLATED(a, 1)) {
                 if (a.memprio & 1) __builtin_amdgcn_s_setprio(3);
-                ols_issue_loads<R, E, T, CPLX>(raw, a, cur, ti);
+                ols_issue_loads<R, E, T, CPLX>(raw, a, cur, t);
                 if (a.memprio & 1) __builtin_amdgcn_s_setprio(0);
             }
         }
@@ -337,22 +235,9 @@ __global__ __launch_bounds__((N / E) * G, MINW) void ols_fused_kernel(OlsFusedAr
             else v[e] = {raw.a[e], raw.b[e]};
         }
         // next unit's samples start streaming from HBM while this unit is transformed
-        if constexpr (PREFETCH) { if (!MDSP_ABLATED(a, 1)) ols_issue_loads<R, E, T, CPLX>(raw, a, nxt, ti); }
+        if constexpr (PREFETCH) { if (!MDSP_ABLATED(a, 1)) ols_issue_loads<R, E, T, CPLX>(raw, a, nxt, t); }
         if (!MDSP_ABLATED(a, 2)) {
-        if constexpr (DMA) {
-            // the forward transform's first pass, by hand: behind its exchange barrier every wave has read `stage`, so the NEXT unit's span
-            // may start to overwrite it -- a whole unit (two transforms) ahead of its use
-            constexpr int BUF0 = 0;
-            cx<R>* region = lds + BUF0 * fft::lds_elems<C::N, PADSHIFT>();
-            fft::pass_compute<C, -1, 0, TWMODE, PADSHIFT, PERM>(v, t, tw, twsrc, region);
-            fft::wg_sync<T>();
-            cur_staged = ols_unit_interior(a, nxt, N);
-            if (cur_staged) ols_dma_issue<T>(a, nxt, N, stage, threadIdx.x);
-            fft::pass_reload<C, PADSHIFT, 1, PERM>(v, t, region);
-            if constexpr (NBUF == 1) fft::wg_sync<T>();
-            fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0, 1, PERM>(v, t, tw, twsrc, lds);
-        } else
-        fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0, 0, PERM>(v, t, tw, twsrc, lds);
+        fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0>(v, t, tw, twsrc, lds);
         // spectral multiply (K2): natural order in registers
         if constexpr (HREG) {
 #pragma unroll
@@ -361,19 +246,19 @@ __global__ __launch_bounds__((N / E) * G, MINW) void ols_fused_kernel(OlsFusedAr
             cx<R> hh[E];
             if constexpr (ROWS) {
                 const __amdgpu_buffer_rsrc_t hrow = io::make_rsrc(static_cast<const cx<R>*>(a.H) + (cur.p % a.hrows) * N, (int64_t)N * (int64_t)sizeof(cx<R>));
-                io::load_window<cx<R>, E, T>(hh, hrow, 0, ti);
+                io::load_window<cx<R>, E, T>(hh, hrow, 0, t);
             } else
-            io::load_window<cx<R>, E, T>(hh, hrsrc, 0, ti);
+            io::load_window<cx<R>, E, T>(hh, hrsrc, 0, t);
 #pragma unroll
             for (int e = 0; e < E; ++e) v[e] = fft::cmul(v[e], hh[e]);
         }
         // inverse transform (unnormalised, like plan_brfft / inv(p).p)
-        fft::wg_fft<C, +1, TWMODE, PADSHIFT, NBUF, (C::P - 1) % NBUF, 0, PERM>(v, t, tw, twsrc, lds);
-        if constexpr (ROWS) {   // conj(W^{k1 (ti + T e)}) = conj(W^{k1 ti} W^{k1 T e}): one table walk per thread and row, E uniform ones (scalar loads)
+        fft::wg_fft<C, +1, TWMODE, PADSHIFT, NBUF, (C::P - 1) % NBUF>(v, t, tw, twsrc, lds);
+        if constexpr (ROWS) {   // conj(W^{k1 (t + T e)}) = conj(W^{k1 t} W^{k1 T e}): one table walk per thread and row, E uniform ones (scalar loads)
             const cx<R>*t0 = static_cast<const cx<R>*>(a.rt0), *t1 = static_cast<const cx<R>*>(a.rt1);
             const unsigned k1 = (unsigned)(cur.p % a.hrows), mask = (1u << a.rlogS) - 1u;
             const auto root = [&](unsigned m) { return fft::cmul(t0[m & mask], t1[m >> a.rlogS]); };
-            const cx<R> w0 = root(k1 * (unsigned)ti);
+            const cx<R> w0 = root(k1 * (unsigned)t);
 #pragma unroll
             for (int e = 0; e < E; ++e) {
                 const cx<R> w = fft::cmul(w0, root(k1 * (unsigned)(T * e)));
@@ -383,19 +268,10 @@ __global__ __launch_bounds__((N / E) * G, MINW) void ols_fused_kernel(OlsFusedAr
         }
         // no barrier needed here: with one buffer wg_fft ends every exchange with a barrier, with two the 2(P-1)
         // exchanges of a unit alternate buffers so the next unit's first write is two barriers behind its readers
-        if constexpr (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next unit's span has landed (issued two transforms ago); BEFORE this
-                                                                              // unit's stores, which the counter would otherwise make us wait for as well
         if (!MDSP_ABLATED(a, 4)) {
-            if constexpr (STAGE && !CPLX && sizeof(R) == 4 && (G == 1 || T == 64) && NBUF == 1 && !PERM) {
-                // wave-uniform (workgroup-uniform: one transform per workgroup, or one-wave transforms): both blocks exist and lie inside y
-                const bool whole = cur.live && (2 * cur.p + 1) < a.nblocks && (2 * cur.p + 2) * a.L <= a.nout;
-                if (whole) ols_store_staged<R, E, T, N>(v, a, cur, ti, reinterpret_cast<float*>(lds));
-                else ols_store<R, E, T, CPLX>(v, a, cur, ti);
-            } else {
-                if (a.memprio & 2) __builtin_amdgcn_s_setprio(3);
-                ols_store<R, E, T, CPLX>(v, a, cur, ti);
-                if (a.memprio & 2) __builtin_amdgcn_s_setprio(0);
-            }
+            if (a.memprio & 2) __builtin_amdgcn_s_setprio(3);
+            ols_store<R, E, T, CPLX>(v, a, cur, t);
+            if (a.memprio & 2) __builtin_amdgcn_s_setprio(0);
         }
         cur = nxt;
     }
@@ -867,10 +743,9 @@ template <typename R> int upload_table(DevBuf& buf, int64_t n) {
 }
 
 // ---- fused launch ---------------------------------------------------------------------------------------
-template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, bool CPLX, int MINW = 2, int NBUF = 2, bool PREFETCH = true, bool HREG = true,
-          int PERM = false, bool STAGE = false, bool XDMA = false, bool ROWS = false>
-int launch_fused_variant(const OlsFusedArgs& a, hipStream_t s) {
-    auto kern = ols_fused_kernel<R, N, E, G, TWMODE, PADSHIFT, CPLX, MINW, NBUF, PREFETCH, HREG, PERM, STAGE, XDMA, ROWS>;
+template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false>
+int launch_fused_geo(const OlsFusedArgs& a, hipStream_t s) {
+    auto kern = ols_fused_kernel<R, N, E, G, TWMODE, CPLX, NBUF, PREFETCH, HREG, ROWS>;
     constexpr int threads = (N / E) * G;
     int per_cu = 0;
     MDSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0));
@@ -908,15 +783,14 @@ int ols_rows_impl(int dbl, void* work, int64_t rows, int hrows, const void* Hrow
     a.rt0 = rt0;
     a.rt1 = rt1;
     a.rlogS = rlogS;
-    //                                                 R   N   E  G TW PAD CPLX MINW NBUF PREF  HREG  PERM  STAGE  XDMA  ROWS
-    if (dbl) return launch_fused_variant<double, 4096, 8, 1, 1, 4, true, 2, 2, false, false, false, false, false, true>(a, st);
-    return launch_fused_variant<float, 8192, 16, 1, 1, 4, true, 2, 1, false, false, false, false, false, true>(a, st);
+    //                                                 R   N   E  G TW CPLX NBUF PREF  HREG  ROWS   (TW: 0 global, 1 regs, 2 LDS)
+    if (dbl) return launch_fused_geo<double, 4096, 8, 1, 1, true, 2, false, false, true>(a, st);
+    return launch_fused_geo<float, 8192, 16, 1, 1, true, 1, false, false, true>(a, st);
 }
 
-template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a, int variant, hipStream_t s) {
+template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a, hipStream_t s) {
     // Geometry: E elements per thread so that a transform owns whole wavefronts (T = N/E >= 64); G transforms
-    // per workgroup so that workgroups have 256 threads where possible.  `variant` selects tuning alternatives
-    // (MDSP_OLS_VARIANT, swept by bench/tune.py); the non-default ones are only built for the headline shape.
+    // per workgroup so that workgroups have 256 threads where possible.
     constexpr bool DBL = sizeof(R) == 8;
     // Elements per thread.  Float32, nfft >= 1024: 16 -- half as many waves per transform (one wave at 1024: no s_barrier at
     // all), measured 6-10 % faster than 8 at nfft = 2048 once the packed-FP32 butterflies removed the register spills
@@ -931,73 +805,28 @@ template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a
 #endif
     // Float64 twiddles: 1 = registers, 0 = global table (registers win even where they spill 84 B: ComplexF64 nfft 4096 85 vs 69 Gsamples/s)
     constexpr int TWREG = DBL ? MDSP_TW_F64 : 1;
-    if constexpr (N == 2048 && !CPLX && !DBL) {
-        switch (variant) {
-            //                                    R  N   E  G  TW PAD CPLX MINW NBUF PREF HREG PERM   (TW: 0 global, 1 regs, 2 LDS)
-            case 2: return launch_fused_variant<R, N, 8, 1, 1, 5, CPLX, 2, 2, true, true, false>(a, s);   // identity lanes, pad 5 (best E = 8 form)
-#ifdef MDSP_DEBUG_KNOBS   // the variants that lost (HISTORY.md section 4.2): only in builds made with -DMDSP_DEBUG_KNOBS
-            case 1: return launch_fused_variant<R, N, 8, 1, 1, 4, CPLX, 2, 2, true, true, false>(a, s);   // identity lanes, pad 4 (previous default)
-            case 10: return launch_fused_variant<R, N, 8, 1, 1, 5, CPLX, 2, 2, true, true, true>(a, s);   // permuted lanes, pad 5
-            case 11: return launch_fused_variant<R, N, 16, 2, 1, 5, CPLX, 2, 1, true, true, false>(a, s);  // E = 16: two waves per transform
-            case 12: return launch_fused_variant<R, N, 16, 2, 1, 4, CPLX, 2, 1, true, true, false>(a, s);  // (= default)
-            case 13: return launch_fused_variant<R, N, 16, 2, 1, 5, CPLX, 2, 2, true, true, false>(a, s);
-            case 3: return launch_fused_variant<R, N, 8, 1, 1, 4, CPLX, 2, 2, true, true, true>(a, s);    // permuted lanes, pad 4
-            case 4: return launch_fused_variant<R, N, 8, 1, 1, 3, CPLX, 2, 2, true, true, false>(a, s);
-            case 5: return launch_fused_variant<R, N, 8, 1, 1, 5, CPLX, 3, 2, true, true, true>(a, s);
-            case 6: return launch_fused_variant<R, N, 8, 1, 0, 5, CPLX, 2, 2, true, true, true>(a, s);    // global twiddles
-            case 7: return launch_fused_variant<R, N, 8, 1, 1, 5, CPLX, 2, 1, true, true, true>(a, s);    // single LDS buffer
-            case 8: return launch_fused_variant<R, N, 8, 1, 1, 5, CPLX, 2, 2, false, true, true>(a, s);   // no prefetch
-            case 9: return launch_fused_variant<R, N, 16, 2, 1, 4, CPLX, 2, 1, true, false, false>(a, s);  // E = 16
-            // register diets for three / four resident workgroups per CU: MINW caps the allocation at 168 / 128 VGPRs
-            case 14: return launch_fused_variant<R, N, 16, 2, 1, 4, CPLX, 3, 1, true, true, false>(a, s);   // registers only, capped at 168
-            case 15: return launch_fused_variant<R, N, 16, 2, 3, 4, CPLX, 3, 1, true, false, false>(a, s);  // hybrid twiddles + spectrum from L2
-            case 16: return launch_fused_variant<R, N, 16, 2, 3, 4, CPLX, 3, 1, true, true, false>(a, s);   // hybrid twiddles, spectrum in registers
-            case 17: return launch_fused_variant<R, N, 16, 2, 2, 4, CPLX, 4, 1, true, false, false>(a, s);  // LDS twiddles + spectrum from L2, capped at 128
-            case 18: return launch_fused_variant<R, N, 16, 2, 2, 4, CPLX, 3, 1, true, false, false>(a, s);  // LDS twiddles + spectrum from L2, capped at 168
-            case 19: return launch_fused_variant<R, N, 16, 2, 3, 4, CPLX, 3, 1, false, false, false>(a, s); // hybrid, L2 spectrum, no prefetch
-            case 23: return launch_fused_variant<R, N, 16, 2, 3, 4, CPLX, 4, 1, false, false, false>(a, s); // same, capped at 128 VGPRs (four workgroups)
-            case 24: return launch_fused_variant<R, N, 16, 2, 0, 4, CPLX, 4, 1, false, false, false>(a, s); // global twiddles, L2 spectrum, no prefetch, 128
-            case 25: return launch_fused_variant<R, N, 16, 2, 3, 5, CPLX, 3, 1, false, false, false>(a, s); // 19 with pad 5
-            case 26: return launch_fused_variant<R, N, 16, 2, 3, 4, CPLX, 3, 1, false, true, false>(a, s);  // hybrid, spectrum in registers, no prefetch
-            case 27: return launch_fused_variant<R, N, 16, 2, 1, 4, CPLX, 3, 1, false, false, false>(a, s); // register twiddles, L2 spectrum, no prefetch
-            case 28: return launch_fused_variant<R, N, 16, 2, 1, 4, CPLX, 2, 1, false, true, false>(a, s);  // default geometry minus the prefetch
-            case 29: return launch_fused_variant<R, N, 16, 1, 3, 4, CPLX, 3, 1, false, true, false>(a, s);  // the default with ONE transform per (128-thread)
-            // workgroup: the two transforms of a 256-thread workgroup share every s_barrier although they exchange nothing
-            case 30: return launch_fused_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, false, true, false>(a, s);  // 28 with one transform per workgroup
-            case 31: return launch_fused_variant<R, N, 16, 1, 3, 4, CPLX, 4, 1, false, false, false>(a, s); // 23 (<= 128 VGPRs, spectrum from L2) with one transform per workgroup
-            case 32: return launch_fused_variant<R, N, 16, 1, 3, 4, CPLX, 3, 1, false, false, false>(a, s); // 19 with one transform per workgroup
-            case 33: return launch_fused_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, true, true, false>(a, s);   // 12 (prefetch) with one transform per workgroup
-            case 34: return launch_fused_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, false, true, false, true>(a, s);   // 30 + outputs staged through LDS, 16-byte stores
-            case 35: return launch_fused_variant<R, N, 16, 1, 3, 4, CPLX, 3, 1, false, true, false, true>(a, s);   // 29 + staged stores
-            case 36: return launch_fused_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, false, true, false, false, true>(a, s);   // 30 + the next unit's span staged in LDS by DMA
-            case 37: return launch_fused_variant<R, N, 16, 1, 3, 4, CPLX, 3, 1, false, true, false, false, true>(a, s);   // 29 (hybrid twiddles, <= 168 VGPRs) + DMA staging
-#endif
-            // DEFAULT (= 30): register twiddles, filter spectrum in registers, no software prefetch, ONE transform per 128-thread workgroup
-            // (191 VGPRs, four workgroups of two waves per CU).  12-round interleaved A/B on two boxes (profiles/r02l_ols_decoupled.json,
-            // r02e_ols_ab.json): 1.85 / 1.78 ms vs 1.93 / 1.86 (29: hybrid twiddles, 3 waves per SIMD) vs 2.05 / 1.97 (26: the same kernel
-            // with two transforms per workgroup) vs 2.17 (12: the round-1 default, prefetch).  Variant 2 is the best E = 8 form; the
-            // lane-permuted schedule (10) has fewer LDS conflicts still, but its permuted global accesses cost more than the LDS cycles it
-            // saves (3.8 vs 4.2 TB/s, profiles/r01e_tune_lanes.json).
-            default: return launch_fused_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, false, true, false>(a, s);
-        }
-    }
+    // The headline shape (real Float32, nfft 2048): register twiddles, filter spectrum in registers, no software prefetch, ONE transform per
+    // 128-thread workgroup (191 VGPRs, four workgroups of two waves per CU) -- the two transforms of a 256-thread workgroup share every
+    // s_barrier although they exchange nothing.  12-round interleaved A/B on two boxes (profiles/r02l_ols_decoupled.json, r02e_ols_ab.json):
+    // 1.85 / 1.78 ms against 2.05 / 1.97 for the same kernel with two transforms per workgroup.
+    if constexpr (N == 2048 && !CPLX && !DBL) return launch_fused_geo<R, N, 16, 1, 1, CPLX, 1, false>(a, s);
     // Software prefetch of the next unit's samples: OFF by default.  Measured on MI355X (profiles/r02c_tune.json, 2^30 Float32, nfft 2048):
     // the same geometry without the prefetch is 14 % faster (1.85 vs 2.16 ms) -- the 32 registers it frees matter less than the issue
     // pattern: loads at the top of the iteration park the wave while its partner workgroup on the SIMD computes, which puts the two
     // resident workgroups in antiphase on their own.  MDSP_OLS_PREFETCH=1 restores the prefetching form (tools/bench_matrix.py sweeps both).
-    if (tunables().ols_prefetch == 1) return launch_fused_variant<R, N, E, G, TWREG, 4, CPLX, 2, NBUF, true>(a, s);
-    return launch_fused_variant<R, N, E, G, TWREG, 4, CPLX, 2, NBUF, false>(a, s);
+    if (tunables().ols_prefetch == 1) return launch_fused_geo<R, N, E, G, TWREG, CPLX, NBUF, true>(a, s);
+    return launch_fused_geo<R, N, E, G, TWREG, CPLX, NBUF, false>(a, s);
 }
 
-template <typename R, bool CPLX> int launch_fused(int64_t nfft, const OlsFusedArgs& a, int variant, hipStream_t s) {
+template <typename R, bool CPLX> int launch_fused(int64_t nfft, const OlsFusedArgs& a, hipStream_t s) {
     switch (nfft) {
-        case 256: return launch_fused_n<R, 256, CPLX>(a, variant, s);
-        case 512: return launch_fused_n<R, 512, CPLX>(a, variant, s);
-        case 1024: return launch_fused_n<R, 1024, CPLX>(a, variant, s);
-        case 2048: return launch_fused_n<R, 2048, CPLX>(a, variant, s);
-        case 4096: return launch_fused_n<R, 4096, CPLX>(a, variant, s);
+        case 256: return launch_fused_n<R, 256, CPLX>(a, s);
+        case 512: return launch_fused_n<R, 512, CPLX>(a, s);
+        case 1024: return launch_fused_n<R, 1024, CPLX>(a, s);
+        case 2048: return launch_fused_n<R, 2048, CPLX>(a, s);
+        case 4096: return launch_fused_n<R, 4096, CPLX>(a, s);
         case 8192:
-            if constexpr (sizeof(R) == 4) return launch_fused_n<R, 8192, CPLX>(a, variant, s);
+            if constexpr (sizeof(R) == 4) return launch_fused_n<R, 8192, CPLX>(a, s);
         default: break;
     }
     MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "fused overlap-save does not support nfft=%lld", (long long)nfft);
@@ -1399,8 +1228,8 @@ static int ols_exec_core(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int6
     a.niter = 0;
     a.ablate = MDSP_DBG(ablate);
     a.memprio = tunables().ols_prio;
-    if (cplx) return dbl ? launch_fused<double, true>(plan->nfft, a, plan->variant, s) : launch_fused<float, true>(plan->nfft, a, plan->variant, s);
-    return dbl ? launch_fused<double, false>(plan->nfft, a, plan->variant, s) : launch_fused<float, false>(plan->nfft, a, plan->variant, s);
+    if (cplx) return dbl ? launch_fused<double, true>(plan->nfft, a, s) : launch_fused<float, true>(plan->nfft, a, s);
+    return dbl ? launch_fused<double, false>(plan->nfft, a, s) : launch_fused<float, false>(plan->nfft, a, s);
 }
 
 int mdsp_ols_exec(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx, void* y_dev, int64_t nout, int64_t ldy,

@@ -31,7 +31,6 @@
 #include "devio.h"
 #include "fft_lds.h"
 #include "fft_wg.h"
-#include "fft_w64.h"
 #include "hostfft.h"
 #include "rocfft_wrap.h"
 #include "welch_plan.h"
@@ -241,7 +240,7 @@ struct SpecArgs {
     int n, nout, onesided;
     int64_t run_len, niter;  // unit schedule: runs of run_len consecutive units per slot, niter iterations per slot
     int ablate;              // profiling aid (MDSP_ABLATE): 1 skip HBM loads, 2 skip transforms, 4 skip accumulate/stores
-    int memprio;             // MDSP_SPEC_PRIO: 1 = a unit's loads (Welch) / loads and stores (STFT) are issued at raised wave priority
+    int memprio;             // MDSP_SPEC_PRIO: bit 0 a Welch unit's loads, bit 1 the STFT column stores are issued at raised wave priority
     int accumulate;          // STFT PSD mode: add to the output column instead of overwriting it (multitaper)
     int ntapers;             // > 0: multitaper PSD in one launch (stft_pair_kernel<MT>): win holds ntapers windows of n doubles, rinv their 1/r
     const double* rinv;
@@ -260,8 +259,8 @@ template <int E, int T> __device__ __forceinline__ void load_window_regs(double 
 // ---- Welch ------------------------------------------------------------------------------------------------
 // SHIFT > 0 (complex signals; host guarantees n == N and hop == SHIFT * T): the samples a frame shares with its predecessor stay
 // in registers, shifted by SHIFT elements per frame -- see stft_fused_kernel.
-template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, bool CPLX, int MINW, int NBUF, bool PREFETCH, bool WIN64, int SHIFT = 0>
-__global__ __launch_bounds__((N / E) * G, MINW) void welch_fused_kernel(SpecArgs a) {
+template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, bool CPLX, int NBUF, bool WIN64, int SHIFT = 0>
+__global__ __launch_bounds__((N / E) * G, 2) void welch_fused_kernel(SpecArgs a) {
     using C = fft::Cfg<N, E>;
     using TT = std::conditional_t<CPLX, cx<R>, R>;
     constexpr int T = C::T;
@@ -333,11 +332,10 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_fused_kernel(SpecArgs
         }
     };
     int64_t u = unit_cur(niter > 0);
-    if constexpr (PREFETCH) issue(u);
+    issue(u);
     for (int64_t it = 0; it < niter; ++it) {
         walk();
         const int64_t unext = unit_cur(it + 1 < niter);
-        if constexpr (!PREFETCH) { if (!MDSP_ABLATED(a, 1)) issue(u); }
         cx<R> v[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) {
@@ -349,7 +347,7 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_fused_kernel(SpecArgs
                 else v[e] = {ra[e] * w[e], rb[e] * w[e]};
             }
         }
-        if constexpr (PREFETCH) { if (!MDSP_ABLATED(a, 1)) issue(unext); }
+        if (!MDSP_ABLATED(a, 1)) issue(unext);   // the next unit's samples stream in while this one is transformed
         u = unext;
         if (!MDSP_ABLATED(a, 2))
         fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0>(v, t, tw, twsrc, lds);
@@ -373,8 +371,8 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_fused_kernel(SpecArgs
 // thread's element e of frame f+1 is its element e + SHIFT of frame f -- the raw samples stay in registers, shift by SHIFT
 // elements per frame, and only the SHIFT new ones are loaded: every sample is read from memory once per run instead of
 // N / hop times (config 4, 75 % overlap: the L2 absorbed only part of the re-reads, PMC fetch 2.3x the input).
-template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, bool CPLX, bool PSD, int MINW, int NBUF, bool PREFETCH, int SHIFT = 0>
-__global__ __launch_bounds__((N / E) * G, MINW) void stft_fused_kernel(SpecArgs a) {
+template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, bool CPLX, bool PSD, int NBUF, int SHIFT = 0>
+__global__ __launch_bounds__((N / E) * G, 2) void stft_fused_kernel(SpecArgs a) {
     using C = fft::Cfg<N, E>;
     using TT = std::conditional_t<CPLX, cx<R>, R>;
     constexpr int T = C::T;
@@ -437,23 +435,18 @@ __global__ __launch_bounds__((N / E) * G, MINW) void stft_fused_kernel(SpecArgs 
         io::load_window<TT, E, T>(ra, r0, 0, t);
     };
     int64_t fcur = unit_cur(niter > 0);
-    if constexpr (PREFETCH) issue(fcur);
+    issue(fcur);
     for (int64_t it = 0; it < niter; ++it) {
         const int64_t f = fcur;
         walk();
         fcur = unit_cur(it + 1 < niter);
-        if constexpr (!PREFETCH) {
-            if (a.memprio & 1) __builtin_amdgcn_s_setprio(3);
-            issue(f);
-            if (a.memprio & 1) __builtin_amdgcn_s_setprio(0);
-        }
         cx<R> v[E];
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             if constexpr (CPLX) v[e] = havewin ? cx<R>{ra[e].x * w[e], ra[e].y * w[e]} : ra[e];
             else v[e] = {havewin ? ra[e] * w[e] : ra[e], (R)0};
         }
-        if constexpr (PREFETCH) issue(fcur);
+        issue(fcur);   // the next frame's samples stream in while this one is transformed
         fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0>(v, t, tw, twsrc, lds);
         if constexpr (C::P > 1 && NBUF > 1 && ((C::P - 1) % NBUF) != 0) fft::wg_sync<T>();  // NBUF == 1: wg_fft already ends every exchange with a barrier
         // column store: bins k = t + T*e < nout, contiguous across lanes
@@ -962,11 +955,8 @@ template <typename R> int welch_finalize(mdsp_welch_plan_s* pl, int64_t K_total,
 // With hop = N/2 the second half of frame a IS the first half of frame b, and the second half of frame b IS the first
 // half of the next unit's frame a.  A slot that walks consecutive units therefore loads every sample exactly ONCE:
 // E loads per thread per unit instead of 2E, and 3E/2 instead of 2E prefetch registers.
-// PREF = false: no software prefetch -- the unit's two new halves are loaded at the top of its iteration and are dead before the transform
-// starts, which frees 16 of the 24 sample registers; latency is covered by a third resident workgroup per CU instead (measured on the
-// overlap-save kernel: +11 % over the prefetching two-workgroup form, profiles/r02b_tune.json).
-template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, int MINW, int NBUF, int PERM = false, bool PREF = true>
-__global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs a) {
+template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, int NBUF>
+__global__ __launch_bounds__((N / E) * G, 2) void welch_half_kernel(SpecArgs a) {
     using C = fft::Cfg<N, E>;
     constexpr int T = C::T;
     constexpr int H = E / 2;
@@ -975,9 +965,7 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs 
     constexpr int REGION = fft::wg_lds_elems<C, PADSHIFT, NBUF>();
     constexpr int64_t SZ = (int64_t)sizeof(R);
     __shared__ __attribute__((aligned(16))) cx<R> lds_all[G * REGION];
-    const int traw = threadIdx.x % T;
-    const int t = fft::io_lane<C, PERM>(traw);     // sample / window ownership before the transform: t + T*e (== traw unless lane-permuted)
-    const int tout = fft::out_lane<C, PERM>(traw);  // bin ownership after it (== t except with the wave-private exchange, PERM == 2)
+    const int t = threadIdx.x % T;   // sample / window ownership before the transform, bin ownership after it: t + T*e
     const int slot = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / T));
     cx<R>* lds = lds_all + slot * REGION;
     const cx<R>* table = static_cast<const cx<R>*>(a.table);
@@ -985,7 +973,7 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs 
 
     cx<R> tw[NTWA];
     __shared__ __attribute__((aligned(16))) cx<R> twl[(TWMODE == fft::TW_LDS || TWMODE == fft::TW_HYB) ? fft::tw_lds_entries<C, TWMODE>() : 1];
-    const cx<R>* twsrc = fft::wg_twiddle_setup<C, TWMODE, PERM>(tw, twl, traw, slot, table);
+    const cx<R>* twsrc = fft::wg_twiddle_setup<C, TWMODE>(tw, twl, t, slot, table);
     R w[E];
     {
         double wd[E];
@@ -997,7 +985,6 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs 
     // partial row every FLUSH units (the reference accumulates in Float32 over ALL frames, periodograms.jl:757; a
     // run of <= 2 FLUSH same-sign terms per lane keeps this far tighter).  Float64: plain double accumulators.
     constexpr bool PAIR = sizeof(R) == 4;
-    constexpr bool SCALAR_ACC = MINW >= 3;   // tighter register budget: one Float32 per bin (two scalar FMAs) instead of a pair
     constexpr int FLUSH = 128;
     cx<R> accp[PAIR ? E : 1];
     double acc[PAIR ? 1 : E];
@@ -1012,8 +999,8 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs 
     const __amdgpu_buffer_rsrc_t prs = io::make_rsrc(part, (int64_t)N * 8);
     int since = 0;
     bool first = true;
-    auto flush = [&]() {   // wave-uniform control flow; per-lane state is one laundered byte offset
-        int off = tout * 8;
+    auto flush = [&, t]() {   // wave-uniform control flow; per-lane state is one laundered byte offset
+        int off = t * 8;
         asm volatile("" : "+v"(off));
         if (first) {
 #pragma unroll
@@ -1043,30 +1030,23 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs 
     };
     const int64_t niter = a.niter;
     // half-frame h of unit u starts at sample u*N + h*(N/2), h = 0 (a lo), 1 (a hi = b lo), 2 (b hi)
-    auto load_half = [&](R (&dst)[H], int64_t u, int h, bool on) {
+    // (both lambdas take t by value: captured by reference it stays in memory until they are inlined, and the transform's address arithmetic is
+    // selected and scheduled differently)
+    auto load_half = [&, t](R (&dst)[H], int64_t u, int h, bool on) {
         const int64_t pos = u * N + (int64_t)h * (N / 2);
         const __amdgpu_buffer_rsrc_t r = io::make_rsrc(sc + pos, on ? std::min<int64_t>(N / 2, a.len - pos) * SZ : 0);
         io::load_window<R, H, T>(dst, r, 0, t);
     };
     R lo[H], ahi[H], bhi[H];
     int64_t u = unit_cur(niter > 0);
-    bool have_lo = false;   // PREF = false: lo[] already holds the first half of unit u (carried over from the previous unit)
-    if constexpr (PREF) {
-        const bool live = u < a.units_per_ch;
-        load_half(lo, u, 0, live);
-        load_half(ahi, u, 1, live);
-        load_half(bhi, u, 2, live && (2 * u + 1) < a.K);
-    }
+    const bool live = u < a.units_per_ch;
+    load_half(lo, u, 0, live);
+    load_half(ahi, u, 1, live);
+    load_half(bhi, u, 2, live && (2 * u + 1) < a.K);
     for (int64_t it = 0; it < niter; ++it) {
         walk();
         const int64_t unext = unit_cur(it + 1 < niter);
         const bool haveB = (2 * u + 1) < a.K;   // u live implied (K >= 1) -- a dead unit has all-zero halves anyway
-        if constexpr (!PREF) {
-            const bool live = u < a.units_per_ch;
-            if (!have_lo) load_half(lo, u, 0, live);
-            load_half(ahi, u, 1, live);
-            load_half(bhi, u, 2, live && haveB);
-        }
         cx<R> v[E];
         if (haveB) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1094,37 +1074,23 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs 
             }
         }
         // next unit: reuse this unit's last half when it is the next frame's first half
-        if constexpr (PREF) {
-            const bool nlive = unext < a.units_per_ch;
-            if (unext == u + 1 && nlive) {
+        const bool nlive = unext < a.units_per_ch;
+        if (unext == u + 1 && nlive) {
 #pragma unroll
-                for (int e = 0; e < H; ++e) lo[e] = bhi[e];
-            } else {
-                load_half(lo, unext, 0, nlive);
-            }
-            load_half(ahi, unext, 1, nlive);
-            load_half(bhi, unext, 2, nlive && (2 * unext + 1) < a.K);
+            for (int e = 0; e < H; ++e) lo[e] = bhi[e];
         } else {
-            have_lo = unext == u + 1 && unext < a.units_per_ch;   // wave-uniform
-            if (have_lo) {
-#pragma unroll
-                for (int e = 0; e < H; ++e) lo[e] = bhi[e];
-            }
+            load_half(lo, unext, 0, nlive);
         }
+        load_half(ahi, unext, 1, nlive);
+        load_half(bhi, unext, 2, nlive && (2 * unext + 1) < a.K);
         u = unext;
         if (!MDSP_ABLATED(a, 2)) {
-            // wave-private last exchange: the workgroup barrier that protects buffer 0 sits HERE, a whole transform after its readers
-            // passed it -- nobody waits at it in steady state
-            if constexpr (PERM == 2) __syncthreads();
-            fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0, 0, PERM>(v, traw, tw, twsrc, lds);
+            fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0>(v, t, tw, twsrc, lds);
             if constexpr (C::P > 1 && NBUF > 1 && ((C::P - 1) % NBUF) != 0) fft::wg_sync<T>();  // NBUF == 1: wg_fft already ends every exchange with a barrier
         }
         if constexpr (PAIR) {
 #pragma unroll
-            for (int e = 0; e < E; ++e) {
-                if constexpr (SCALAR_ACC) accp[e].x = v[e].x * v[e].x + (v[e].y * v[e].y + accp[e].x);
-                else accp[e] = fft::lanefma(v[e], v[e], accp[e]);
-            }
+            for (int e = 0; e < E; ++e) accp[e] = fft::lanefma(v[e], v[e], accp[e]);
             if (++since == FLUSH) flush();
         } else {
 #pragma unroll
@@ -1135,7 +1101,7 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs 
         flush();
     } else {
 #pragma unroll
-        for (int e = 0; e < E; ++e) part[tout + T * e] = acc[e];
+        for (int e = 0; e < E; ++e) part[t + T * e] = acc[e];
     }
 }
 
@@ -1150,28 +1116,22 @@ __global__ __launch_bounds__((N / E) * G, MINW) void welch_half_kernel(SpecArgs 
 //     folded by the finalize kernel anyway), so the roles of the two pair arrays and of their halves alternate from unit to unit (loop unrolled x2);
 //   * the window rides in the first butterfly stage (fft::bfly16_win: 8 packed operations less), and the butterflies' constant roots come
 //     from SGPR pairs (fft_lds.h, MDSP_FFT_SGPR_CONST).
-//   * DEEP: the samples of the next TWO units are in flight instead of one.  The phase profile of the one-deep form (profiles/r03b_welch_phases.txt)
-//     showed a wave parked ~1000 of a unit's ~5250 clocks in front of the first butterfly stage, waiting for loads it had issued one unit
-//     (~3300 clocks, 1.5 us) earlier: with two workgroups per CU and one unit (16 KiB) in flight per workgroup -- and only between issue
-//     and arrival -- a CU keeps ~20 KiB outstanding, and Little's law (bytes in flight = bandwidth x latency, ~2 us under load) caps the
-//     kernel near 3 TB/s whatever the arithmetic does.  Two register sets alternate; the half-frame hand-over is replaced by a third
-//     (L2-hit) load so that a unit's pairs do not depend on its predecessor's registers.
-template <int N, int PADSHIFT, int NBUF, bool DEEP = false>
+template <int N>
 __global__ __launch_bounds__(N / 16, 2) void welch_half3_kernel(SpecArgs a) {
     using R = float;
-    constexpr int E = 16, H = 8;
+    constexpr int E = 16, H = 8, PADSHIFT = 5;   // one LDS buffer, one element of padding per 32
     using C = fft::Cfg<N, E>;
     constexpr int T = C::T;
     static_assert(T % 64 == 0 && T >= 128, "one transform per workgroup");
     constexpr int NTWA = C::NTW > 0 ? C::NTW : 1;
-    constexpr int REGION = fft::wg_lds_elems<C, PADSHIFT, NBUF>();
+    constexpr int REGION = fft::wg_lds_elems<C, PADSHIFT, 1>();
     __shared__ __attribute__((aligned(16))) cx<R> lds[REGION];
     const int t = threadIdx.x;
     const cx<R>* table = static_cast<const cx<R>*>(a.table);
     const int64_t ch = blockIdx.y;
 
     cx<R> tw[NTWA];
-    fft::load_twiddles<C, R, 1, fft::TW_REG, false>(tw, t, table);
+    fft::load_twiddles<C, R, 1, fft::TW_REG>(tw, t, table);
     cx<R> wp[H];   // {w[t + T e], w[t + T (e + 8)]}
     {
         double wd[E];
@@ -1263,23 +1223,23 @@ __global__ __launch_bounds__(N / 16, 2) void welch_half3_kernel(SpecArgs a) {
 #ifdef MDSP_WELCH_PROF
         // phase timeline of one unit (debug builds: build.py --tag prof --cflags -DMDSP_WELCH_PROF): shader-clock stamps at the phase boundaries,
         // summed per wave; s_memtime needs lgkmcnt(0), which every boundary here waits for anyway (barriers, first use of the reloaded operands)
-        static_assert(C::P == 3 && NBUF == 1, "the phase profile is wired for three passes and one LDS buffer");
+        static_assert(C::P == 3, "the phase profile is wired for three passes");
         MDSP_STAMP(1);   // pass 0: butterflies + LDS writes done, next unit's loads issued
         fft::wg_sync<T>();
         MDSP_STAMP(2);   // barrier 1
-        fft::pass_reload<C, PADSHIFT, 1, 0>(v, t, lds);
+        fft::pass_reload<C, PADSHIFT>(v, t, lds);
         MDSP_STAMP(3);   // operands of pass 1 back from LDS
         fft::wg_sync<T>();
         MDSP_STAMP(4);   // barrier 2
-        fft::pass_compute<C, -1, 1, fft::TW_REG, PADSHIFT, 0>(v, t, tw, table, lds);
+        fft::pass_compute<C, -1, 1, fft::TW_REG, PADSHIFT>(v, t, tw, table, lds);
         MDSP_STAMP(5);   // pass 1 + LDS writes
         fft::wg_sync<T>();
         MDSP_STAMP(6);   // barrier 3
-        fft::pass_reload<C, PADSHIFT, 2, 0>(v, t, lds);
+        fft::pass_reload<C, PADSHIFT>(v, t, lds);
         MDSP_STAMP(7);   // operands of pass 2
         fft::wg_sync<T>();
         MDSP_STAMP(8);   // barrier 4
-        fft::pass_compute<C, -1, 2, fft::TW_REG, PADSHIFT, 0>(v, t, tw, table, lds);
+        fft::pass_compute<C, -1, 2, fft::TW_REG, PADSHIFT>(v, t, tw, table, lds);
 #pragma unroll
         for (int e = 0; e < E; ++e) accp[e] = fft::lanefma(v[e], v[e], accp[e]);
         asm volatile("" :: "v"(accp[0].x), "v"(accp[E - 1].y));
@@ -1289,74 +1249,40 @@ __global__ __launch_bounds__(N / 16, 2) void welch_half3_kernel(SpecArgs a) {
         ++prof_units;
 #else
         fft::wg_sync<T>();
-        fft::pass_reload<C, PADSHIFT, 1, 0>(v, t, lds);
-        if constexpr (NBUF == 1) fft::wg_sync<T>();
-        fft::wg_fft<C, -1, fft::TW_REG, PADSHIFT, NBUF, 0, 1, 0>(v, t, tw, table, lds);
-        if constexpr (C::P > 1 && NBUF > 1 && ((C::P - 1) % NBUF) != 0) fft::wg_sync<T>();
+        fft::pass_reload<C, PADSHIFT>(v, t, lds);
+        fft::wg_sync<T>();
+        fft::wg_fft<C, -1, fft::TW_REG, PADSHIFT, 1, 0, 1>(v, t, tw, table, lds);
 #pragma unroll
         for (int e = 0; e < E; ++e) accp[e] = fft::lanefma(v[e], v[e], accp[e]);
         if (++since == FLUSH) flush();
 #endif
     };
-    if constexpr (!DEEP) {
-        auto unit = [&](cx<R> (&Q)[H], cx<R> (&F)[H], bool xa, bool more) {
-            walk();
-            const int64_t unext = unit_cur(more);
+    auto unit = [&](cx<R> (&Q)[H], cx<R> (&F)[H], bool xa, bool more) {
+        walk();
+        const int64_t unext = unit_cur(more);
 #ifdef MDSP_WELCH_PROF
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            MDSP_STAMP(10);   // this unit's samples have arrived
-            {
-                cx<R> v0[16];
-                fft::bfly16_win<-1>(Q, F, wp, v0);
-                asm volatile("" :: "v"(v0[0].x), "v"(v0[15].y));
-                MDSP_STAMP(11);   // first pass: arithmetic
-                fft::pass0_scatter<C, PADSHIFT>(v0, t, lds);
-                MDSP_STAMP(12);   // first pass: LDS writes retired
-            }
-#else
-            fft::pass0_windowed<C, PADSHIFT>(Q, F, wp, t, lds);   // consumes Q and F
-#endif
-            // the successor: F's frame-b-second-half component is its frame a's first half when it follows directly (roles and halves swap)
-            const bool carry = unext == u + 1 && unext < a.units_per_ch;   // wave-uniform
-            load_unit(F, Q, !xa, unext, carry);
-            u = unext;
-            tail();
-        };
-        for (int64_t it = 0; it < a.niter; it += 2) {   // same trip count for every slot (barriers inside)
-            unit(P1, P2, true, it + 1 < a.niter);
-            if (it + 1 < a.niter) unit(P2, P1, false, it + 2 < a.niter);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        MDSP_STAMP(10);   // this unit's samples have arrived
+        {
+            cx<R> v0[16];
+            fft::bfly16_win<-1>(Q, F, wp, v0);
+            asm volatile("" :: "v"(v0[0].x), "v"(v0[15].y));
+            MDSP_STAMP(11);   // first pass: arithmetic
+            fft::pass0_scatter<C, PADSHIFT>(v0, t, lds);
+            MDSP_STAMP(12);   // first pass: LDS writes retired
         }
-    } else {
-        // two register sets, both with frame a in .x; a set is refilled with the unit TWO ahead as soon as the first stage has consumed it
-        cx<R> P3[H], P4[H];
-        int64_t taken = 1;   // (P1, P2) hold the slot's first unit
-        auto take = [&]() {
-            walk();
-            return unit_cur(taken++ < a.niter);
-        };
-        load_unit(P3, P4, true, take(), false);
-        auto unit_deep = [&](cx<R> (&Q)[H], cx<R> (&F)[H]) {
-#ifdef MDSP_WELCH_PROF
-            asm volatile("s_waitcnt vmcnt(32)" ::: "memory");   // this unit's 32 loads are the older half of what is in flight
-            MDSP_STAMP(10);
-            {
-                cx<R> v0[16];
-                fft::bfly16_win<-1>(Q, F, wp, v0);
-                asm volatile("" :: "v"(v0[0].x), "v"(v0[15].y));
-                MDSP_STAMP(11);
-                fft::pass0_scatter<C, PADSHIFT>(v0, t, lds);
-                MDSP_STAMP(12);
-            }
 #else
-            fft::pass0_windowed<C, PADSHIFT>(Q, F, wp, t, lds);
+        fft::pass0_windowed<C, PADSHIFT>(Q, F, wp, t, lds);   // consumes Q and F
 #endif
-            load_unit(Q, F, true, take(), false);
-            tail();
-        };
-        for (int64_t it = 0; it < a.niter; it += 2) {
-            unit_deep(P1, P2);
-            if (it + 1 < a.niter) unit_deep(P3, P4);
-        }
+        // the successor: F's frame-b-second-half component is its frame a's first half when it follows directly (roles and halves swap)
+        const bool carry = unext == u + 1 && unext < a.units_per_ch;   // wave-uniform
+        load_unit(F, Q, !xa, unext, carry);
+        u = unext;
+        tail();
+    };
+    for (int64_t it = 0; it < a.niter; it += 2) {   // same trip count for every slot (barriers inside)
+        unit(P1, P2, true, it + 1 < a.niter);
+        if (it + 1 < a.niter) unit(P2, P1, false, it + 2 < a.niter);
     }
     flush();
 #ifdef MDSP_WELCH_PROF
@@ -1370,162 +1296,8 @@ __global__ __launch_bounds__(N / 16, 2) void welch_half3_kernel(SpecArgs a) {
 #endif
 }
 
-// ---- the same path with the samples staged in LDS by DMA (round 3) ----------------------------------------------------------------------
-// Phase profile of welch_half3_kernel (profiles/r03c_welch_phases.txt): of a unit's ~5300 clocks a wave spends ~700 ISSUING its 32
-// buffer_load_dword (a wave instruction moves 256 bytes, and the four waves of a workgroup reach the load burst together) and ~800 waiting for
-// them, however early they were issued (two units ahead changes nothing) -- 28 % of the unit in a load path built from 4-byte-per-lane
-// instructions.  Here a unit's two new half-frames (2 x 8 KiB) arrive by buffer_load_dwordx4 ... lds: four DMA instructions per wave and unit
-// instead of 32 loads, no VGPRs, issued two units ahead.  Half-frame k of the channel lives in ring slot k mod 5 (5 x 8 KiB next to the 33 KiB
-// exchange buffer: two workgroups per CU still fit); unit u reads half-frames 2u, 2u+1, 2u+2 as the (frame a, frame b) pairs of the first stage
-// and, once every wave is past the first exchange barrier (all reads of the two oldest slots done), its waves refill those two slots with the
-// half-frames of unit u+2.  Every wave issues the same number of DMA instructions per unit (a zero-size descriptor for half-frames that do not
-// exist), so "all but the newest batch have landed" is the constant s_waitcnt vmcnt(4), placed in front of an exchange barrier that exists
-// anyway: the pipeline adds no barrier.  One contiguous run of units per slot (the default schedule); other schedules take welch_half3_kernel.
-template <int N, int PADSHIFT>
-__global__ __launch_bounds__(N / 16, 2) void welch_half4_kernel(SpecArgs a) {
-    using R = float;
-    constexpr int E = 16, H = 8, NBUF = 1, NSLOT = 5;
-    using C = fft::Cfg<N, E>;
-    constexpr int T = C::T, NW = T / 64;
-    constexpr int HALF = N / 2;                      // samples per half-frame
-    constexpr int GRAN = HALF / 256;                 // 1 KiB DMA granules per half-frame
-    static_assert(T % 64 == 0 && T >= 128 && C::P == 3 && GRAN % NW == 0, "geometry");
-    constexpr int GPW = GRAN / NW;                   // granules per wave and half-frame
-    constexpr int NTWA = C::NTW > 0 ? C::NTW : 1;
-    constexpr int REGION = fft::wg_lds_elems<C, PADSHIFT, NBUF>();
-    __shared__ __attribute__((aligned(16))) cx<R> lds[REGION];
-    __shared__ __attribute__((aligned(16))) R ring[NSLOT * HALF];
-    const int t = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(t / 64), lane = t & 63;
-    const cx<R>* table = static_cast<const cx<R>*>(a.table);
-    const int64_t ch = blockIdx.y;
-
-    cx<R> tw[NTWA];
-    fft::load_twiddles<C, R, 1, fft::TW_REG, false>(tw, t, table);
-    cx<R> wp[H];
-    {
-        double wd[E];
-        load_window_regs<E, T>(wd, a.win, a.n, t);
-#pragma unroll
-        for (int e = 0; e < H; ++e) wp[e] = {(R)wd[e], (R)wd[e + H]};
-    }
-    constexpr int FLUSH = 128;
-    cx<R> accp[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) accp[e] = {(R)0, (R)0};
-    double* part = static_cast<double*>(a.out) + ((int64_t)blockIdx.x * a.nch + ch) * N;
-    const __amdgpu_buffer_rsrc_t prs = io::make_rsrc(part, (int64_t)N * 8);
-    int since = 0;
-    bool first = true;
-    auto flush = [&]() {
-        int off = t * 8;
-        asm volatile("" : "+v"(off));
-        if (first) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) io::Ld<double>::store((double)accp[e].x + (double)accp[e].y, prs, off + T * e * 8);
-        } else {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const double s = io::Ld<double>::load(prs, off + T * e * 8) + ((double)accp[e].x + (double)accp[e].y);
-                io::Ld<double>::store(s, prs, off + T * e * 8);
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < E; ++e) accp[e] = {(R)0, (R)0};
-        first = false;
-        since = 0;
-    };
-
-    const R* sc = static_cast<const R*>(a.s) + ch * a.lds_;
-    // this slot's units: u0 .. u0 + cnt - 1 (consecutive; run_len covers the slot's whole share), dead iterations behind them
-    const int64_t u0 = (int64_t)blockIdx.x * a.run_len;
-    const int64_t uend = std::min<int64_t>(u0 + a.run_len, a.units_per_ch);           // one past this slot's last live unit
-    // half-frame k (of the channel) is wanted by this slot iff it belongs to a frame of one of its units: k in [2 u0, klast]
-    const int64_t klast = uend > u0 ? 2 * (uend - 1) + (((2 * (uend - 1) + 1) < a.K) ? 2 : 1) : -1;
-    const unsigned ring0 = io::lds_byte_address(ring);
-    // this wave's share of half-frame k -> ring slot k mod NSLOT (always GPW instructions: an unwanted half-frame moves nothing)
-    auto dma_half = [&](int64_t k, int slot) {
-        const bool want = k >= 2 * u0 && k <= klast;
-        const io::dma_i4 r = io::dma_rsrc(sc + k * HALF, want ? (long long)HALF * 4 : 0);
-#pragma unroll
-        for (int g = 0; g < GPW; ++g) {
-            const int gr = wave * GPW + g;
-            io::dma256(r, ring0 + (unsigned)slot * (unsigned)(HALF * 4) + (unsigned)gr * 1024u, gr * 1024 + lane * 16);
-        }
-    };
-    // prologue: unit u0 (three half-frames) and unit u0 + 1 (two more) -- slots 0 .. 4; then only the newest batch (GPW x 2) may be outstanding
-    dma_half(2 * u0, 0); dma_half(2 * u0 + 1, 1); dma_half(2 * u0 + 2, 2);
-    dma_half(2 * u0 + 3, 3); dma_half(2 * u0 + 4, 4);
-    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * GPW) : "memory");
-    __syncthreads();
-    int s0 = 0;                                      // ring slot of half-frame 2 u (wave-uniform)
-    int64_t u = u0;
-    for (int64_t it = 0; it < a.niter; ++it, ++u) {  // same trip count for every slot (barriers inside)
-        const bool live = u < uend, haveB = live && (2 * u + 1) < a.K;
-        const int s1 = s0 + 1 >= NSLOT ? s0 + 1 - NSLOT : s0 + 1, s2 = s0 + 2 >= NSLOT ? s0 + 2 - NSLOT : s0 + 2;
-        cx<R> Q[H], F[H];                            // Q = (a lo | b lo), F = (a hi | b hi)
-        if (live) {
-            const R* h0 = ring + s0 * HALF + t;
-            const R* h1 = ring + s1 * HALF + t;
-            const R* h2 = ring + s2 * HALF + t;
-#pragma unroll
-            for (int e = 0; e < H; ++e) {
-                const R m = h1[T * e];
-                Q[e] = {h0[T * e], m};
-                F[e] = {m, h2[T * e]};
-            }
-            if (!haveB) {                            // the odd last frame of the channel: no frame b
-#pragma unroll
-                for (int e = 0; e < H; ++e) {
-                    Q[e].y = (R)0;
-                    F[e].y = (R)0;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < H; ++e) Q[e] = F[e] = {(R)0, (R)0};
-        }
-        fft::pass0_windowed<C, PADSHIFT>(Q, F, wp, t, lds);
-        cx<R> v[E];
-        fft::wg_sync<T>();                           // exchange barrier 1: every wave has read its half-frames
-        // refill the two oldest slots with the half-frames of unit u + 2
-        dma_half(2 * u + 5, s0);
-        dma_half(2 * u + 6, s1);
-        fft::pass_reload<C, PADSHIFT, 1, 0>(v, t, lds);
-        fft::wg_sync<T>();
-        fft::pass_compute<C, -1, 1, fft::TW_REG, PADSHIFT, 0>(v, t, tw, table, lds);
-        fft::wg_sync<T>();
-        fft::pass_reload<C, PADSHIFT, 2, 0>(v, t, lds);
-        // all but the batch just issued has landed (this wave's share); behind the barrier the next unit's half-frames are complete
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * GPW) : "memory");
-        fft::wg_sync<T>();
-        fft::pass_compute<C, -1, 2, fft::TW_REG, PADSHIFT, 0>(v, t, tw, table, lds);
-#pragma unroll
-        for (int e = 0; e < E; ++e) accp[e] = fft::lanefma(v[e], v[e], accp[e]);
-        if (++since == FLUSH) flush();
-        s0 = s2;
-    }
-    flush();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // nothing of this workgroup may still be writing its LDS when it exits
-}
-
-template <int N, int PADSHIFT> int welch_run_half4(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int* nslices) {
-    auto kern = welch_half4_kernel<N, PADSHIFT>;
-    constexpr int threads = N / 16;
-    int grid = 1;
-    MDSP_TRY(grid_for(kern, threads, a.units_per_ch, a.nch, &grid));
-    MDSP_TRY(pl->partial.reserve(sizeof(double) * (size_t)grid * (size_t)a.nch * N));
-    a.out = pl->partial.p;
-    set_schedule(a, a.units_per_ch, (int64_t)grid);
-    if (a.run_len * (int64_t)grid < a.units_per_ch) return -1000;   // several runs per slot (MDSP_RUNS_PER_SLOT): the caller takes welch_half3_kernel
-    hipLaunchKernelGGL(kern, dim3(grid, (unsigned)a.nch), dim3(threads), 0, st, a);
-    MDSP_LAUNCH_CHECK();
-    *nslices = grid;
-    return MDSP_OK;
-}
-
-template <int N, int PADSHIFT, int NBUF, bool DEEP = false> int welch_run_half3(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int* nslices) {
-    auto kern = welch_half3_kernel<N, PADSHIFT, NBUF, DEEP>;
+template <int N> int welch_run_half3(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int* nslices) {
+    auto kern = welch_half3_kernel<N>;
     constexpr int threads = N / 16;
     int grid = 1;
     MDSP_TRY(grid_for(kern, threads, a.units_per_ch, a.nch, &grid));
@@ -1571,11 +1343,11 @@ template <int N, int PADSHIFT, int NBUF, bool DEEP = false> int welch_run_half3(
     return MDSP_OK;
 }
 
-#include "welch_w64.h"   // one wavefront per transform (round 4): welch_w64_kernel, welch_run_w64
+#include "welch_w64.h"   // one wavefront per transform: the hand-allocated kernels and welch_run_w64asm
 
-template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, int MINW, int NBUF, int PERM = false, bool PREF = true>
+template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, int NBUF>
 int welch_run_half(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int* nslices) {
-    auto kern = welch_half_kernel<R, N, E, G, TWMODE, PADSHIFT, MINW, NBUF, PERM, PREF>;
+    auto kern = welch_half_kernel<R, N, E, G, TWMODE, PADSHIFT, NBUF>;
     constexpr int threads = (N / E) * G;
     int grid = 1;
     MDSP_TRY(grid_for(kern, threads, cdiv(a.units_per_ch, G), a.nch, &grid));
@@ -1588,9 +1360,9 @@ int welch_run_half(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int* nsli
     return MDSP_OK;
 }
 
-template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, bool CPLX, int MINW, int NBUF, bool PREFETCH, bool WIN64, int SHIFT = 0>
-int welch_run_variant(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int* nslices) {
-    auto kern = welch_fused_kernel<R, N, E, G, TWMODE, PADSHIFT, CPLX, MINW, NBUF, PREFETCH, WIN64, SHIFT>;
+template <typename R, int N, int E, int G, int TWMODE, int PADSHIFT, bool CPLX, int NBUF, bool WIN64, int SHIFT = 0>
+int welch_run_fused(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st, int* nslices) {
+    auto kern = welch_fused_kernel<R, N, E, G, TWMODE, PADSHIFT, CPLX, NBUF, WIN64, SHIFT>;
     constexpr int threads = (N / E) * G;
     int grid = 1;
     MDSP_TRY(grid_for(kern, threads, cdiv(a.units_per_ch, G), a.nch, &grid));
@@ -1617,112 +1389,51 @@ int welch_launch_n(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st) {
     int nslices = 0, rc = MDSP_OK;
     const bool half_ok = !CPLX && a.n == N && 2 * a.hop == N && !MDSP_DBG(welch_nohalf);
     if constexpr (!CPLX && N >= 256) {
-        if (half_ok && !(N == 4096 && sizeof(R) == 4 && pl->variant >= 1 && pl->variant <= 9)) {
-            constexpr int EH = (N >= 2048 && sizeof(R) == 4) ? 16 : Gm::E;   // Float32, nfft >= 1024: 16 elements per thread (Geo does 1024)
-            constexpr int GH = slots_per_workgroup(N / EH);
-            constexpr int NB = (N / EH) <= 64 ? 1 : 2;
-            constexpr int NBH = (EH == 16) ? 1 : NB;
-            bool done = false;
-            if constexpr (N == 4096 && sizeof(R) == 4) {  // tuning alternatives of the headline shape (MDSP_WELCH_VARIANT)
-                done = true;
-                //                                              R  N  E   G  TW PAD MINW NBUF
-                // product builds: 18 (the round-2 form: identity lanes, pad 5), 30 (welch_half3_kernel, the default below the hand-allocated kernel's stream
-                // length), 43 (mdsp_welch_w64c_asm) and 44 (mdsp_welch_w64d_asm, the default); every other variant lost its A/B (HISTORY.md section 4.3) and
-                // is built with -DMDSP_DEBUG_KNOBS only
-                if (pl->variant == 18) rc = welch_run_half<R, N, EH, GH, 1, 5, 2, 1, false>(pl, a, st, &nslices);   // identity lanes, pad 5
-                else if (pl->variant == 30) rc = welch_run_half3<N, 5, 1>(pl, a, st, &nslices);   // round 3: paired samples, branch-free, window in the first stage
-                else if (pl->variant == 43 || pl->variant == 44) {   // ... the same, hand-allocated, shared half-frame carried (csrc/welch_w64c_asm.s, and
-                    bool handled = false;                             // csrc/welch_w64d_asm.s with folded twiddles): reduces into pl->reduced itself
-                    rc = w64::welch_run_w64asm(pl, a, st, &handled, pl->variant);
-                    if (rc == MDSP_OK && handled) goto reduced_done;
-                }
-#ifdef MDSP_DEBUG_KNOBS
-                else if (pl->variant == 10) rc = welch_run_half<R, N, EH, GH, 1, 4, 2, 1>(pl, a, st, &nslices);        // identity lanes, pad 4 (previous default)
-                else if (pl->variant == 11) rc = welch_run_half<R, N, EH, GH, 1, 4, 2, 2>(pl, a, st, &nslices);
-                else if (pl->variant == 19) rc = welch_run_half<R, N, EH, GH, 1, 5, 2, 2, true>(pl, a, st, &nslices);    // permuted, two LDS buffers
-                else if (pl->variant == 20) rc = welch_run_half<R, N, EH, GH, 1, 5, 2, 1, true>(pl, a, st, &nslices);    // permuted lanes, pad 5
-                else if (pl->variant == 21) rc = welch_run_half<R, N, EH, GH, 1, 5, 2, 2, false>(pl, a, st, &nslices);   // identity lanes, pad 5, two LDS buffers
-                else if (pl->variant == 22) rc = welch_run_half<R, N, EH, GH, 1, 4, 2, 2, 2>(pl, a, st, &nslices);       // wave-private last exchange (one real barrier per transform)
-                else if (pl->variant == 23) rc = welch_run_half<R, N, EH, GH, 1, 5, 2, 1, 0, false>(pl, a, st, &nslices);   // registers, no prefetch (still two workgroups)
-                else if (pl->variant == 24) rc = welch_run_half<R, N, EH, GH, 3, 5, 3, 1, 0, false>(pl, a, st, &nslices);   // hybrid twiddles, scalar accumulators, <= 168 VGPRs
-                else if (pl->variant == 25) rc = welch_run_half<R, N, EH, GH, 3, 4, 3, 1, 0, false>(pl, a, st, &nslices);   // same, pad 4
-                else if (pl->variant == 26) rc = welch_run_half<R, N, EH, GH, 2, 5, 3, 1, 0, false>(pl, a, st, &nslices);   // LDS twiddles
-                else if (pl->variant == 27) rc = welch_run_half<R, N, EH, GH, 3, 5, 3, 1, 0, true>(pl, a, st, &nslices);    // hybrid + prefetch (= 16 with pad 5)
-                else if (pl->variant == 12) rc = welch_run_half<R, N, EH, GH, 2, 4, 2, 1>(pl, a, st, &nslices);
-                else if (pl->variant == 13) rc = welch_run_half<R, N, 8, 1, 1, 4, 2, 2>(pl, a, st, &nslices);
-                else if (pl->variant == 14) rc = welch_run_half<R, N, 8, 1, 1, 4, 4, 2>(pl, a, st, &nslices);
-                else if (pl->variant == 15) rc = welch_run_half<R, N, 8, 1, 1, 4, 4, 1>(pl, a, st, &nslices);
-                else if (pl->variant == 16) rc = welch_run_half<R, N, EH, GH, 3, 4, 3, 1>(pl, a, st, &nslices);
-                else if (pl->variant == 17) rc = welch_run_half<R, N, EH, GH, 3, 4, 2, 1>(pl, a, st, &nslices);
-                else if (pl->variant == 31) rc = welch_run_half3<N, 5, 2>(pl, a, st, &nslices);   // ... with two LDS buffers (one barrier per exchange)
-                else if (pl->variant == 32) rc = welch_run_half3<N, 4, 1>(pl, a, st, &nslices);   // ... pad 4
-                else if (pl->variant == 33) rc = welch_run_half3<N, 5, 1, true>(pl, a, st, &nslices);   // ... two units in flight (two register sets)
-                else if (pl->variant == 34) rc = welch_run_half3<N, 4, 1, true>(pl, a, st, &nslices);
-                else if (pl->variant == 41) rc = w64::welch_run_w64b(pl, a, st, &nslices);  // ... two waves per SIMD: two-level twiddles, direct loads
-                else if (pl->variant == 40) rc = w64::welch_run_w64(pl, a, st, &nslices);   // round 4: one wavefront per transform, 64 x 64, one exchange
-                else if (pl->variant == 35 || pl->variant == 36) {   // half-frames staged in LDS by DMA, two units ahead (pad 5 / pad 4)
-                    rc = pl->variant == 35 ? welch_run_half4<N, 5>(pl, a, st, &nslices) : welch_run_half4<N, 4>(pl, a, st, &nslices);
-                    if (rc == -1000) rc = welch_run_half3<N, 5, 1>(pl, a, st, &nslices);
-                }
-#endif
-                else done = false;
-            }
-            if (!done) {
-                if constexpr (N == 4096 && sizeof(R) == 4) {
-                    // Round 3 default: welch_half3_kernel (paired samples, branch-free, window in the first stage: 17 % fewer vector instructions).
-                    // The kernel runs AT the 1400 W package power cap (profiles/r03e_power_probe.json), so what the diet buys is energy: 1.4-2.3 %
-                    // less time in sustained runs, nothing measurable in short bursts (profiles/r03a_tune_new.json).  MDSP_WELCH_VARIANT=18 is the
-                    // round-2 kernel (identity lanes, pad 5); several runs per slot (MDSP_RUNS_PER_SLOT) work in both.
-                    // Round 4: streams long enough to give every wave of the chip a unit take the hand-allocated one-wavefront-per-transform kernel
-                    // (csrc/welch_w64c_asm.s = variant 43, the form that carries the shared half-frame: 1.00 against 1.17 ms on an all-zero stream,
-                    // 1.22 against 1.34 under the power cap, HBM traffic 1.01 x algorithmic; profiles/r04_welch_carry_power.json; variant 42 is the
-                    // first form, which re-reads that half-frame); MDSP_WELCH_VARIANT=30 keeps welch_half3_kernel.
-                    // Round 7: csrc/welch_w64d_asm.s = variant 44, variant 43 with 13 % fewer vector instructions (folded twiddles): 1.275 against 1.356 ms, the stage
-                    // -5.1 %, filt +1.0 % in the same steps (profiles/r07_welch_w64d_ab.json); 43 stays selectable.
-                    if (a.K / 2 >= (int64_t)device_cu_count() * 8 && tunables().runs_per_slot == 1) {
+        if (half_ok) {
+            if constexpr (N == 4096 && sizeof(R) == 4) {
+                // The headline shape has four kernels, selectable with MDSP_WELCH_VARIANT when the plan is made:
+                //   44 csrc/welch_w64d_asm.s: hand-allocated, one wavefront per transform, the half-frame two units share carried in registers, folded
+                //      twiddles.  It reduces into pl->reduced itself.  The default where the stream is long enough to give every wave of the chip a
+                //      unit and the schedule is one run per slot (MDSP_RUNS_PER_SLOT); 30 is the default otherwise.
+                //   43 csrc/welch_w64c_asm.s: the same kernel before the twiddles were folded (13 % more vector instructions; 1.356 against 1.275 ms,
+                //      profiles/r07_welch_w64d_ab.json).  The tests compare 44 against it.
+                //   30 welch_half3_kernel: the HIP kernel for every other stream length and schedule (1.17 against 1.00 ms for 43 on an all-zero
+                //      stream, profiles/r04_welch_carry_power.json).
+                //   18 welch_half_kernel with pad shift 5: the generic half-frame kernel, the reference the tests hold 30 and 43 against.
+                // Any other number selects the default rule.
+                if (pl->variant == 18) rc = welch_run_half<R, N, 16, 1, 1, 5, 1>(pl, a, st, &nslices);
+                else {
+                    const bool long_enough = a.K / 2 >= (int64_t)device_cu_count() * 8 && tunables().runs_per_slot == 1;
+                    if (pl->variant == 43 || pl->variant == 44 || (pl->variant != 30 && long_enough)) {
                         bool handled = false;
-                        rc = w64::welch_run_w64asm(pl, a, st, &handled, 44);
+                        rc = w64::welch_run_w64asm(pl, a, st, &handled, pl->variant == 43 ? 43 : 44);
                         if (rc == MDSP_OK && handled) goto reduced_done;
                         if (rc != MDSP_OK) return rc;
                     }
-                    rc = welch_run_half3<N, 5, 1>(pl, a, st, &nslices);
+                    rc = welch_run_half3<N>(pl, a, st, &nslices);
                 }
-                else
-                    rc = welch_run_half<R, N, EH, GH, Gm::TWREG, pad_default<R>(), 2, NBH>(pl, a, st, &nslices);
+            } else {
+                constexpr int EH = (N >= 2048 && sizeof(R) == 4) ? 16 : Gm::E;   // Float32, nfft >= 1024: 16 elements per thread (Geo does 1024)
+                constexpr int GH = slots_per_workgroup(N / EH);
+                constexpr int NBH = (EH == 16 || N / EH <= 64) ? 1 : 2;
+                rc = welch_run_half<R, N, EH, GH, Gm::TWREG, pad_default<R>(), NBH>(pl, a, st, &nslices);
             }
             goto finalize;
         }
     }
-    if constexpr (N == 4096 && !CPLX && sizeof(R) == 4) {
-#ifdef MDSP_DEBUG_KNOBS
-        switch (pl->variant) {  // tuning alternatives (MDSP_WELCH_VARIANT), built for the headline shape only
-            //                                  R  N   E  G TW PAD CPLX MINW NBUF PREF WIN64      (TW: 0 global, 1 regs, 2 LDS)
-            case 1: rc = welch_run_variant<R, N, 16, 1, 1, 4, CPLX, 2, 2, true, false>(pl, a, st, &nslices); break;
-            case 2: rc = welch_run_variant<R, N, 16, 1, 1, 4, CPLX, 2, 2, false, false>(pl, a, st, &nslices); break;
-            case 3: rc = welch_run_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, true, false>(pl, a, st, &nslices); break;
-            case 4: rc = welch_run_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, false, false>(pl, a, st, &nslices); break;
-            case 5: rc = welch_run_variant<R, N, 16, 1, 2, 4, CPLX, 2, 1, true, false>(pl, a, st, &nslices); break;
-            case 6: rc = welch_run_variant<R, N, 16, 1, 2, 4, CPLX, 2, 1, false, false>(pl, a, st, &nslices); break;
-            case 7: rc = welch_run_variant<R, N, 16, 1, 1, 5, CPLX, 2, 2, false, false>(pl, a, st, &nslices); break;
-            case 8: rc = welch_run_variant<R, N, 8, 1, 1, 4, CPLX, 4, 2, false, false>(pl, a, st, &nslices); break;
-            case 9: rc = welch_run_variant<R, N, 8, 1, 1, 4, CPLX, 2, 2, false, false>(pl, a, st, &nslices); break;
-            case 10: rc = welch_run_variant<R, N, 8, 1, 1, 4, CPLX, 2, 2, true, false>(pl, a, st, &nslices); break;
-            default: rc = welch_run_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, true, false>(pl, a, st, &nslices); break;
-        }
-#else
-        rc = welch_run_variant<R, N, 16, 1, 1, 4, CPLX, 2, 1, true, false>(pl, a, st, &nslices);
-#endif
+    if constexpr (N == 4096 && !CPLX && sizeof(R) == 4) {   // the headline shape off the half-frame path: 16 elements per thread, one LDS buffer
+        rc = welch_run_fused<R, N, 16, 1, 1, 4, CPLX, 1, false>(pl, a, st, &nslices);
     } else {
         bool done = false;
         if constexpr (CPLX && sizeof(R) == 4 && Gm::E > 4) {   // complex Float32 frames advancing by whole elements: overlap stays in registers
             constexpr int T = N / Gm::E;
             const int shift = (!MDSP_DBG(stft_noshift) && a.n == N && a.hop % T == 0 && a.hop / T < Gm::E) ? (int)(a.hop / T) : 0;
             done = shift == 1 || shift == 2 || shift == 4;
-            if (shift == 1) rc = welch_run_variant<R, N, Gm::E, Gm::G, Gm::TWREG, pad_default<R>(), CPLX, 2, Gm::NBUF, true, false, 1>(pl, a, st, &nslices);
-            else if (shift == 2) rc = welch_run_variant<R, N, Gm::E, Gm::G, Gm::TWREG, pad_default<R>(), CPLX, 2, Gm::NBUF, true, false, 2>(pl, a, st, &nslices);
-            else if (shift == 4) rc = welch_run_variant<R, N, Gm::E, Gm::G, Gm::TWREG, pad_default<R>(), CPLX, 2, Gm::NBUF, true, false, 4>(pl, a, st, &nslices);
+            if (shift == 1) rc = welch_run_fused<R, N, Gm::E, Gm::G, Gm::TWREG, pad_default<R>(), CPLX, Gm::NBUF, false, 1>(pl, a, st, &nslices);
+            else if (shift == 2) rc = welch_run_fused<R, N, Gm::E, Gm::G, Gm::TWREG, pad_default<R>(), CPLX, Gm::NBUF, false, 2>(pl, a, st, &nslices);
+            else if (shift == 4) rc = welch_run_fused<R, N, Gm::E, Gm::G, Gm::TWREG, pad_default<R>(), CPLX, Gm::NBUF, false, 4>(pl, a, st, &nslices);
         }
-        if (!done) rc = welch_run_variant<R, N, Gm::E, Gm::G, Gm::TWREG, pad_default<R>(), CPLX, 2, Gm::NBUF, true, sizeof(R) == 8>(pl, a, st, &nslices);
+        if (!done) rc = welch_run_fused<R, N, Gm::E, Gm::G, Gm::TWREG, pad_default<R>(), CPLX, Gm::NBUF, sizeof(R) == 8>(pl, a, st, &nslices);
     }
 finalize:
     if (rc != MDSP_OK) return rc;
@@ -2114,38 +1825,6 @@ template <typename R, int N, bool CPLX> int stft_launch_n(mdsp_stft_plan_s* pl, 
         MDSP_LAUNCH_CHECK();
         return MDSP_OK;
     };
-    if constexpr (N == 1024 && sizeof(R) == 4 && CPLX) {   // tuning alternatives of the config-4 shape (MDSP_STFT_VARIANT)
-        // default for this shape: one wavefront per transform (E = 16, T = 64, four transforms per workgroup, no s_barrier
-        // at all) -- measured 7-11 % faster than the two-wave E = 8 geometry (variant 9).  Variants 2-4: global twiddles.
-        const int variant = tunables().stft_variant;
-        if (variant >= 1 && variant <= 4) {
-            constexpr int E2 = 16, G2 = 4, T2 = 64;
-            const int64_t work2 = cdiv(a.K, G2);
-            auto run2 = [&](auto kern) -> int {
-                MDSP_TRY(grid_for(kern, T2 * G2, work2, a.nch, &grid));
-                set_schedule(a, a.K, (int64_t)grid * G2);
-                hipLaunchKernelGGL(kern, dim3(grid, (unsigned)a.nch), dim3(T2 * G2), 0, st, a);
-                MDSP_LAUNCH_CHECK();
-                return MDSP_OK;
-            };
-            if (variant == 1) {
-                // register reuse of the overlapping samples when a frame advances by a whole number of elements per thread
-                const int shift = (!MDSP_DBG(stft_noshift) && a.n == N && a.hop % T2 == 0) ? (int)(a.hop / T2) : 0;
-#define MDSP_STFT_V1(S) (pl->psd_only ? run2(stft_fused_kernel<R, N, E2, G2, 1, 4, CPLX, true, 2, 1, true, S>) : run2(stft_fused_kernel<R, N, E2, G2, 1, 4, CPLX, false, 2, 1, true, S>))
-                switch (shift) {
-                    case 1: return MDSP_STFT_V1(1);
-                    case 2: return MDSP_STFT_V1(2);
-                    case 4: return MDSP_STFT_V1(4);
-                    case 8: return MDSP_STFT_V1(8);
-                    default: return MDSP_STFT_V1(0);
-                }
-#undef MDSP_STFT_V1
-            }
-            if (variant == 2) return pl->psd_only ? run2(stft_fused_kernel<R, N, E2, G2, 0, 4, CPLX, true, 2, 1, true>) : run2(stft_fused_kernel<R, N, E2, G2, 0, 4, CPLX, false, 2, 1, true>);
-            if (variant == 3) return pl->psd_only ? run2(stft_fused_kernel<R, N, E2, G2, 0, 5, CPLX, true, 2, 1, true>) : run2(stft_fused_kernel<R, N, E2, G2, 0, 5, CPLX, false, 2, 1, true>);
-            return pl->psd_only ? run2(stft_fused_kernel<R, N, E2, G2, 0, 4, CPLX, true, 3, 1, true>) : run2(stft_fused_kernel<R, N, E2, G2, 0, 4, CPLX, false, 3, 1, true>);
-        }
-    }
     if constexpr (!CPLX) {
         // real signals: two frames per transform (stft_pair_kernel); MDSP_STFT_NOPAIR=1 keeps the one-frame-per-transform kernel
         const bool nopair = MDSP_DBG(stft_nopair);
@@ -2168,17 +1847,20 @@ template <typename R, int N, bool CPLX> int stft_launch_n(mdsp_stft_plan_s* pl, 
         constexpr int T = N / E;
         const int shift = (!MDSP_DBG(stft_noshift) && a.n == N && a.hop % T == 0 && a.hop / T < E) ? (int)(a.hop / T) : 0;
 #define MDSP_STFT_GEN(S) \
-    (pl->psd_only ? run(stft_fused_kernel<R, N, E, G, TWREG, pad_default<R>(), CPLX, true, 2, NBUF, true, S>) \
-                  : run(stft_fused_kernel<R, N, E, G, TWREG, pad_default<R>(), CPLX, false, 2, NBUF, true, S>))
+    (pl->psd_only ? run(stft_fused_kernel<R, N, E, G, TWREG, pad_default<R>(), CPLX, true, NBUF, S>) \
+                  : run(stft_fused_kernel<R, N, E, G, TWREG, pad_default<R>(), CPLX, false, NBUF, S>))
         if constexpr (E > 4) {
             if (shift == 1) return MDSP_STFT_GEN(1);
             if (shift == 2) return MDSP_STFT_GEN(2);
             if (shift == 4) return MDSP_STFT_GEN(4);
         }
+        if constexpr (E > 8) {   // nfft 1024: one wavefront per transform (Geo), 16 elements per thread
+            if (shift == 8) return MDSP_STFT_GEN(8);
+        }
 #undef MDSP_STFT_GEN
     }
-    if (pl->psd_only) return run(stft_fused_kernel<R, N, E, G, TWREG, pad_default<R>(), CPLX, true, 2, NBUF, true>);
-    return run(stft_fused_kernel<R, N, E, G, TWREG, pad_default<R>(), CPLX, false, 2, NBUF, true>);
+    if (pl->psd_only) return run(stft_fused_kernel<R, N, E, G, TWREG, pad_default<R>(), CPLX, true, NBUF>);
+    return run(stft_fused_kernel<R, N, E, G, TWREG, pad_default<R>(), CPLX, false, NBUF>);
 }
 
 template <typename R, bool CPLX>

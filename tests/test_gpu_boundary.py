@@ -888,16 +888,15 @@ def test_polyphase_nonfinite_samples_leave_the_reference_hole(d, torch, L, M, nt
     assert outs["regtap"][1] != 2                                  # MDSP_FIR_MM=0 never takes the matrix-core kernel
 
 
-@pytest.mark.parametrize("variant", [30, 31, 32, 33, 34, 35, 36, 40, 41, 43])
+@pytest.mark.parametrize("variant", [30, 43])
 def test_welch_round3_kernel_vs_oracle_and_round2_kernel(d, torch, variant):
-    """welch_half3_kernel (paired samples, role-swapping units, window folded into the first butterfly stage, frame b's first half loaded a
-    second time under the unit's have-frame-b predicate): every frame count parity, the odd last frame, one to three frames, several
-    channels, a stream long enough for the Float64 fold (FLUSH = 128 units) and for slots that walk several runs -- against the oracle and
-    against the round-2 kernel (same frames, same accumulators; only the rounding of the first stage differs)."""
+    """welch_half3_kernel (variant 30: paired samples, role-swapping units, window folded into the first butterfly stage, frame b's first half
+    loaded a second time under the unit's have-frame-b predicate) and the hand-allocated one-wavefront kernel that carries the shared half-frame
+    (variant 43): every frame count parity, the odd last frame, one to three frames, several channels, a stream long enough for the Float64
+    fold (FLUSH = 128 units) and for slots that walk several runs -- against the oracle and against the round-2 kernel (variant 18: same frames,
+    same accumulators; only the rounding of the first stage differs)."""
     from dsp_jl_amd import _lib
     from oracle import periodograms as opg, windows as ow
-    if variant not in (30, 43) and not _lib.lib().mdsp_debug_knobs():
-        pytest.skip("product builds keep the default (43), its fallback (30) and the round-2 form (18); the variants that lost are built with -DMDSP_DEBUG_KNOBS only")
     rng = np.random.default_rng(300 + variant)
     try:
         for length in (4096, 6144, 8191, 8192, 10240, 12288, 100_000, 4096 * 700 + 2048, (1 << 23) + 4097):
@@ -1192,49 +1191,6 @@ def test_host_pipeline_polyphase_filter(d, torch):
     assert isinstance(y_host, np.ndarray) and np.array_equal(y_host, y_dev.cpu().numpy())
     r_host = d.resample(x, ratio)
     assert np.array_equal(r_host, d.resample(torch.from_numpy(x).cuda(), ratio).cpu().numpy())
-
-
-@pytest.mark.parametrize("variant", [36, 37])
-def test_overlap_save_lds_dma_staging_is_bit_identical(d, torch, variant):
-    from dsp_jl_amd import _lib as _l
-    if not _l.lib().mdsp_debug_knobs():
-        pytest.skip("variants 36 / 37 lost their A/B and are built with -DMDSP_DEBUG_KNOBS only (round 5)")
-    """ols_fused_kernel<..., XDMA>: the next unit's span goes HBM -> LDS by buffer_load ... lds while this unit is transformed.  Only WHERE the
-    samples wait changes, so outputs must equal the direct-load kernel bit for bit: signals of every edge shape (shorter than a block, one unit,
-    an odd block count, leading zero padding, the clamped tail), several columns (units of different columns alternate in a slot), conv mode
-    (blocks past the end of x), block ranges from a slice (mdsp_ols_exec_range), and a long stream whose slots walk many interior units."""
-    from dsp_jl_amd import _lib
-    from dsp_jl_amd.dspbase import OlsPlan
-    from oracle import dspbase as odsp
-    rng = np.random.default_rng(360 + variant)
-    lib = _lib.lib()
-    b = _taps(256, np.float32)
-    try:
-        for nx, ncols, mode in ((100, 1, _lib.OLS_FILT), (1793, 1, _lib.OLS_FILT), (3586, 1, _lib.OLS_FILT), (3587, 2, _lib.OLS_FILT), (10_000, 3, _lib.OLS_FILT),
-                                (1_000_003, 1, _lib.OLS_FILT), (700_001, 2, _lib.OLS_CONV), ((1 << 24) + 12345, 1, _lib.OLS_FILT), (3_000_000, 5, _lib.OLS_FILT)):
-            x = torch.from_numpy(rng.standard_normal((ncols, nx)).astype(np.float32)).cuda()
-            nout = nx if mode == _lib.OLS_FILT else nx + 255
-            _lib.set_tunable("MDSP_OLS_VARIANT", "0")
-            ref = OlsPlan(b, 2048, nx, mode, d.ENGINE_FUSED).exec(x, nout)
-            _lib.set_tunable("MDSP_OLS_VARIANT", str(variant))
-            plan = OlsPlan(b, 2048, nx, mode, d.ENGINE_FUSED)
-            got = plan.exec(x, nout)
-            torch.cuda.synchronize()
-            assert torch.equal(got, ref), (variant, nx, ncols, mode)
-            assert torch.equal(plan.exec(x, nout), ref)                       # and again: the staging buffer carries nothing over between launches
-            if nx == 1_000_003:
-                want = odsp.filt_ba(b.astype(np.float64), 1.0, x[0, :60000].cpu().numpy().astype(np.float64))
-                assert relerr(got[0, :60000].cpu().numpy(), want) < TOL32
-                # a block range from a slice of the signal (host pipeline / time-axis split): blocks [100, 300) of the same grid
-                L, g0, g1 = 1793, 100, 300
-                lo, hi = g0 * L - 255, g1 * L
-                xs = x[0, lo:hi].contiguous()
-                ys = torch.empty(hi - g0 * L, dtype=torch.float32, device="cuda")
-                _lib.check(lib.mdsp_ols_exec_range(plan._h, xs.data_ptr(), lo, hi - lo, nx, ys.data_ptr(), g0, g1 - g0, nx, None))
-                torch.cuda.synchronize()
-                assert torch.equal(ys, ref[0, g0 * L:hi])
-    finally:
-        _lib.set_tunable("MDSP_OLS_VARIANT", None)
 
 
 @pytest.mark.parametrize("nfft", [1000, 1200, 1280, 1500, 1536, 1600, 1920, 2000, 2400, 2500, 2560, 3000, 3072, 3200, 3840, 4000, 4800, 5000, 5120, 6000, 6144, 6400, 8000])

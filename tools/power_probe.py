@@ -3,7 +3,7 @@
 shader clock, the power cap), and reports average power / clock / time per launch: the Welch kernel on random data, on an all-zero stream (no
 toggling: the DVFS give-back of MI355X_MICROARCH.md), the overlap-save kernel, and the float4 copy.  Writes gpurun_out/power_probe.json.
 
-    python tools/power_probe.py [LOG2N=30] [SECONDS=3] [WELCH_VARIANTS=0,30,35]
+    python tools/power_probe.py [LOG2N=30] [SECONDS=3] [WELCH_VARIANTS=0,30,43]
 """
 import ctypes as C
 import json
@@ -27,7 +27,7 @@ lib = _lib.lib()
 _lib.check(lib.mdsp_init(0))
 n = 1 << int(os.environ.get("LOG2N", "30"))
 secs = float(os.environ.get("SECONDS", "3"))
-wvars = [int(v) for v in os.environ.get("WELCH_VARIANTS", "0,30,35").split(",")]
+wvars = [int(v) for v in os.environ.get("WELCH_VARIANTS", "0,30,43").split(",")]
 g = torch.Generator(device="cuda"); g.manual_seed(1776)
 x = torch.randn(n, generator=g, device="cuda", dtype=torch.float32)
 xz = torch.zeros_like(x)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Sweep the tuning variants of the fused kernels on the GPU box (within-process, interleaved rounds) and write
-gpurun_out/tune.json.  Variants are selected at plan creation through MDSP_OLS_VARIANT / MDSP_WELCH_VARIANT."""
+the timings as tune.json (the last lines of this file say where).  Variants are selected at plan creation: MDSP_WELCH_VARIANT (18, 30, 43, 44;
+0 = the default rule) for the Welch kernel; MDSP_OLS_VARIANT steers partitioned overlap-save plans only (tools/bench_longfilt.py),
+the fused kernel timed here has one form."""
 import ctypes as C
 import json
 import os
@@ -42,7 +44,7 @@ def timeit(fn):
 
 res = {"log2n": log2n, "ols": {}, "welch": {}, "stft": {}}
 # ---- overlap-save ----
-ols_variants = [int(v) for v in os.environ.get("TUNE_OLS", "0,1,2,3,4,5,6,7,8,9,10,11,12").split(",") if v != ""]
+ols_variants = [int(v) for v in os.environ.get("TUNE_OLS", "0").split(",") if v != ""]
 plans = {}
 for v in ols_variants:
     _lib.set_tunable("MDSP_OLS_VARIANT", str(v))
@@ -66,7 +68,7 @@ for k, v in res["ols"].items():
     v["median_ms"] = sorted(v["ms"])[len(v["ms"]) // 2]
 del plans, ref
 # ---- Welch ----
-welch_variants = [int(v) for v in os.environ.get("TUNE_WELCH", "0,1,2,3,4,5,6,7,8,9").split(",") if v != ""]
+welch_variants = [int(v) for v in os.environ.get("TUNE_WELCH", "0,18,30,43,44").split(",") if v != ""]
 cfgs = {}
 for v in welch_variants:
     _lib.set_tunable("MDSP_WELCH_VARIANT", str(v))
