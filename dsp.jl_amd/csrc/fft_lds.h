@@ -64,6 +64,28 @@ template <typename R> MDSP_HD cx<R> cscale_k(R h, cx<R> u) { return cscale(h, u)
 template <typename R> MDSP_HD cx<R> caxpy_k(R h, cx<R> u, cx<R> e) { return caxpy(h, u, e); }
 template <typename R> MDSP_HD cx<R> caxmy_k(R h, cx<R> u, cx<R> e) { return caxmy(h, u, e); }
 
+// ---- folds.  A product W b whose value only feeds the pair (a + W b, a - W b) is never formed: it rides in the pair,
+//     t = a + b.y (-W.y, W.x),    plus = t + b.x W,    minus = 2 a - plus
+// three multiply-adds where product, add and subtract take four.  `minus` carries the roundings of `plus` and one of its own (the note at
+// bfly16_win applies).  W = w for DIR < 0, conj(w) for DIR > 0.  These are the scalar forms, one fused multiply-add per packed half in the order
+// of the packed Float32 forms below (tests/cpu_harness/fold_emul.cpp runs them on the host).
+MDSP_HD float fma1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+MDSP_HD double fma1(double a, double b, double c) { return __builtin_fma(a, b, c); }
+template <typename R> struct cx2 {
+    cx<R> plus, minus;
+};
+template <int DIR, typename R> MDSP_HD cx2<R> fold(cx<R> a, cx<R> b, cx<R> w) {
+    const R wy = DIR < 0 ? w.y : -w.y;
+    const cx<R> t = {fma1(b.y, -wy, a.x), fma1(b.y, w.x, a.y)};
+    const cx<R> p = {fma1(b.x, w.x, t.x), fma1(b.x, wy, t.y)};
+    return {p, {fma1(a.x, (R)2, -p.x), fma1(a.y, (R)2, -p.y)}};
+}
+// the reduced forms: W = -+i (one add, one subtract), and W = h u / |u| for an unscaled u (W8 = h (1 -+ i), W8^3 = -h (1 +- i): two multiply-adds)
+template <int DIR, typename R> MDSP_HD cx2<R> fold_mi(cx<R> a, cx<R> b) { return {add_mi<DIR>(a, b), sub_mi<DIR>(a, b)}; }
+template <typename R> MDSP_HD cx2<R> fold_re(cx<R> a, R h, cx<R> u) {
+    return {{fma1(u.x, h, a.x), fma1(u.y, h, a.y)}, {fma1(-u.x, h, a.x), fma1(-u.y, h, a.y)}};
+}
+
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(MDSP_NO_PACKED_F32)
 // ---------------------------------------------------------------------------------- packed-FP32 complex arithmetic
 // gfx950 issues v_pk_{add,mul,fma}_f32 at the rate of their scalar forms, and a complex number IS a (lo, hi) register
@@ -282,6 +304,96 @@ template <int DIR> __device__ __forceinline__ void bfly4(cx<float>& a0, cx<float
 }
 #endif
 
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MDSP_NO_PACKED_F32) && MDSP_PK_FUSED
+// The folded radix-4 butterflies (see fold above; the scalar forms further down say what each computes) as ONE statement each: the three
+// multiply-adds of a fold are  FA: t = a + b.y (-+w.y, w.x),  FB: plus = t + b.x (w.x, +-w.y),  F2: minus = 2 a - plus  (2.0 is an inline constant).
+#define MDSP_M_SUB " neg_lo:[0,1] neg_hi:[0,1]"
+#define MDSP_M_ADD_IB " op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]"
+#define MDSP_M_SUB_IB " op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]"
+#define MDSP_M_YY " op_sel:[1,1] op_sel_hi:[1,0]"
+#define MDSP_M_FIN_F " op_sel_hi:[0,1,1] neg_lo:[0,0,1]"
+#define MDSP_M_FIN_I " op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
+#define MDSP_M_FA_F " op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
+#define MDSP_M_FA_I " op_sel:[1,1,0] op_sel_hi:[1,0,1]"
+#define MDSP_M_FB_F " op_sel_hi:[0,1,1]"
+#define MDSP_M_FB_I " op_sel_hi:[0,1,1] neg_hi:[0,1,0]"
+#define MDSP_M_F2 " op_sel_hi:[1,0,1] neg_lo:[0,0,1] neg_hi:[0,0,1]"
+#define MDSP_M_NEGA " neg_lo:[1,0,0] neg_hi:[1,0,0]"
+// a2, a3 lack their twiddles w2, w3.  %0..%3 = a0..a3, %4 %5 temporaries, %6 %7 = w2 w3; X0 lands in %0, X1 in %4, X2 in %1, X3 in %3
+#define MDSP_BFLY4_TW(FA, FB, X1, X3)                                                                                         \
+    asm("v_pk_fma_f32 %4, %2, %6, %0" FA "\n\tv_pk_fma_f32 %5, %3, %7, %1" FA "\n\t"                                            \
+        "v_pk_fma_f32 %4, %2, %6, %4" FB "\n\tv_pk_fma_f32 %5, %3, %7, %5" FB "\n\t"              /* %4 = T0, %5 = T2 */        \
+        "v_pk_fma_f32 %2, %0, 2.0, %4" MDSP_M_F2 "\n\tv_pk_fma_f32 %3, %1, 2.0, %5" MDSP_M_F2 "\n\t" /* %2 = T1, %3 = D */       \
+        "v_pk_add_f32 %0, %4, %5\n\tv_pk_add_f32 %1, %4, %5" MDSP_M_SUB "\n\t"                                                  \
+        "v_pk_add_f32 %4, %2, %3" X1 "\n\tv_pk_add_f32 %3, %2, %3" X3                                                           \
+        : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "=&v"(t), "=&v"(u) : "v"(f2v{w2.x, w2.y}), "v"(f2v{w3.x, w3.y}))
+template <int DIR, int WDIR> __device__ __forceinline__ void bfly4_tw(cx<float>& a0, cx<float>& a1, cx<float>& a2, cx<float>& a3, cx<float> w2, cx<float> w3) {
+    f2v r0 = {a0.x, a0.y}, r1 = {a1.x, a1.y}, r2 = {a2.x, a2.y}, r3 = {a3.x, a3.y}, t, u;
+    if constexpr (DIR < 0 && WDIR < 0) MDSP_BFLY4_TW(MDSP_M_FA_F, MDSP_M_FB_F, MDSP_M_SUB_IB, MDSP_M_ADD_IB);
+    else if constexpr (DIR < 0) MDSP_BFLY4_TW(MDSP_M_FA_I, MDSP_M_FB_I, MDSP_M_SUB_IB, MDSP_M_ADD_IB);
+    else if constexpr (WDIR < 0) MDSP_BFLY4_TW(MDSP_M_FA_F, MDSP_M_FB_F, MDSP_M_ADD_IB, MDSP_M_SUB_IB);
+    else MDSP_BFLY4_TW(MDSP_M_FA_I, MDSP_M_FB_I, MDSP_M_ADD_IB, MDSP_M_SUB_IB);
+    a0 = {r0.x, r0.y};
+    a1 = {t.x, t.y};
+    a2 = {r1.x, r1.y};
+    a3 = {r3.x, r3.y};
+}
+#undef MDSP_BFLY4_TW
+// Column q = 1 and q = 3 of the radix-16 butterfly's outer stage: a1 W16^A formed, a2 times +-W8-ish as u = a2 -+ i a2 scaled by h inside T0 / T1,
+// a3 W16^B folded.  %0..%3 = a0..a3, %4 %5 temporaries, %6 = W16^A, %7 = (h, h), %8 = W16^B (constants, in VGPR pairs: the one user, ols.hip, keeps them there); X0 in %0, X1 in %1, X2 in %4, X3 in %3
+#define MDSP_BFLY4_W16_13(FIN, UMOD, T0NEG, T1NEG, FA, FB, X1, X3)                                                              \
+    asm("v_pk_mul_f32 %4, %1, %6" MDSP_M_YY "\n\tv_pk_add_f32 %5, %2, %2" UMOD "\n\t"                                             \
+        "v_pk_fma_f32 %4, %1, %6, %4" FIN "\n\t"                                                  /* %4 = a1 W16^A */            \
+        "v_pk_fma_f32 %1, %5, %7, %0" T0NEG "\n\tv_pk_fma_f32 %2, %5, %7, %0" T1NEG "\n\t"         /* %1 = T0, %2 = T1 */         \
+        "v_pk_fma_f32 %5, %3, %8, %4" FA "\n\tv_pk_fma_f32 %5, %3, %8, %5" FB "\n\t"               /* %5 = T2 */                  \
+        "v_pk_fma_f32 %3, %4, 2.0, %5" MDSP_M_F2 "\n\t"                                           /* %3 = D */                   \
+        "v_pk_add_f32 %0, %1, %5\n\tv_pk_add_f32 %4, %1, %5" MDSP_M_SUB "\n\t"                                                    \
+        "v_pk_add_f32 %1, %2, %3" X1 "\n\tv_pk_add_f32 %3, %2, %3" X3                                                             \
+        : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "=&v"(t), "=&v"(u) : "v"(f2v{wa.x, wa.y}), "v"(f2v{h, h}), "v"(f2v{wb.x, wb.y}))
+// Column q = 2: a1 W8 formed, a2 (-+i) and a3 W8^3 folded.  %6 = (h, h); X0 in %5, X1 in %1, X2 in %4, X3 in %3
+#define MDSP_BFLY4_W16_2(MI_ADD, MI_SUB)                                                                                         \
+    asm("v_pk_add_f32 %4, %1, %1" MI_ADD "\n\tv_pk_add_f32 %5, %3, %3" MI_SUB "\n\t"                                              \
+        "v_pk_mul_f32 %4, %4, %6\n\t"                                                             /* %4 = a1 W8 */               \
+        "v_pk_add_f32 %1, %0, %2" MI_ADD "\n\tv_pk_add_f32 %2, %0, %2" MI_SUB "\n\t"               /* %1 = T0, %2 = T1 */         \
+        "v_pk_fma_f32 %0, %5, %6, %4" MDSP_M_NEGA "\n\tv_pk_fma_f32 %3, %5, %6, %4\n\t"            /* %0 = T2, %3 = D */          \
+        "v_pk_add_f32 %5, %1, %0\n\tv_pk_add_f32 %4, %1, %0" MDSP_M_SUB "\n\t"                                                    \
+        "v_pk_add_f32 %1, %2, %3" MI_ADD "\n\tv_pk_add_f32 %3, %2, %3" MI_SUB                                                     \
+        : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3), "=&v"(t), "=&v"(u) : "v"(f2v{h, h}))
+template <int DIR, int Q> __device__ __forceinline__ void bfly4_w16(cx<float>& a0, cx<float>& a1, cx<float>& a2, cx<float>& a3) {
+    constexpr float c1 = 0.92387953251128675612818318939679f, s1 = 0.38268343236508977172845998403040f, h = 0.70710678118654752440084436210485f;
+    constexpr cx<float> wa = Q == 1 ? cx<float>{c1, -s1} : cx<float>{s1, -c1}, wb = Q == 1 ? cx<float>{s1, -c1} : cx<float>{-c1, s1};
+    f2v r0 = {a0.x, a0.y}, r1 = {a1.x, a1.y}, r2 = {a2.x, a2.y}, r3 = {a3.x, a3.y}, t, u;
+    if constexpr (Q == 2) {
+        if constexpr (DIR < 0) MDSP_BFLY4_W16_2(MDSP_M_SUB_IB, MDSP_M_ADD_IB);
+        else MDSP_BFLY4_W16_2(MDSP_M_ADD_IB, MDSP_M_SUB_IB);
+        a0 = {u.x, u.y};
+    } else {
+        if constexpr (Q == 1 && DIR < 0) MDSP_BFLY4_W16_13(MDSP_M_FIN_F, MDSP_M_SUB_IB, "", MDSP_M_NEGA, MDSP_M_FA_F, MDSP_M_FB_F, MDSP_M_SUB_IB, MDSP_M_ADD_IB);
+        else if constexpr (Q == 1) MDSP_BFLY4_W16_13(MDSP_M_FIN_I, MDSP_M_ADD_IB, "", MDSP_M_NEGA, MDSP_M_FA_I, MDSP_M_FB_I, MDSP_M_ADD_IB, MDSP_M_SUB_IB);
+        else if constexpr (DIR < 0) MDSP_BFLY4_W16_13(MDSP_M_FIN_F, MDSP_M_ADD_IB, MDSP_M_NEGA, "", MDSP_M_FA_F, MDSP_M_FB_F, MDSP_M_SUB_IB, MDSP_M_ADD_IB);
+        else MDSP_BFLY4_W16_13(MDSP_M_FIN_I, MDSP_M_SUB_IB, MDSP_M_NEGA, "", MDSP_M_FA_I, MDSP_M_FB_I, MDSP_M_ADD_IB, MDSP_M_SUB_IB);
+        a0 = {r0.x, r0.y};
+    }
+    a1 = {r1.x, r1.y};
+    a2 = {t.x, t.y};
+    a3 = {r3.x, r3.y};
+}
+#undef MDSP_BFLY4_W16_13
+#undef MDSP_BFLY4_W16_2
+#undef MDSP_M_SUB
+#undef MDSP_M_ADD_IB
+#undef MDSP_M_SUB_IB
+#undef MDSP_M_YY
+#undef MDSP_M_FIN_F
+#undef MDSP_M_FIN_I
+#undef MDSP_M_FA_F
+#undef MDSP_M_FA_I
+#undef MDSP_M_FB_F
+#undef MDSP_M_FB_I
+#undef MDSP_M_F2
+#undef MDSP_M_NEGA
+#endif
+
 // natural-order in, natural-order out
 template <int DIR, typename R> MDSP_HD void bfly4(cx<R>& a0, cx<R>& a1, cx<R>& a2, cx<R>& a3) {
     const cx<R> t0 = cadd(a0, a2), t1 = csub(a0, a2), t2 = cadd(a1, a3), d = csub(a1, a3);
@@ -295,11 +407,9 @@ template <int DIR, typename R> MDSP_HD void bfly4(cx<R>& a0, cx<R>& a1, cx<R>& a
 template <int DIR, typename R> MDSP_HD cx<R> w8_1_unscaled(cx<R> o) { return add_mi<DIR>(o, o); }
 template <int DIR, typename R> MDSP_HD cx<R> w8_3_unscaled_neg(cx<R> o) { return sub_mi<DIR>(o, o); }
 
-template <int DIR, typename R> MDSP_HD void bfly8(cx<R> (&v)[8]) {
+// everything of the radix-8 butterfly after the even / odd radix-4 sub-transforms (E[k] in v[2k], O[k] in v[2k+1])
+template <int DIR, typename R> MDSP_HD void bfly8_tail(cx<R> (&v)[8]) {
     constexpr R h = (R)0.70710678118654752440084436210485L;
-    // even / odd radix-4 sub-transforms: E[k] lands in v[2k], O[k] in v[2k+1]
-    bfly4<DIR>(v[0], v[2], v[4], v[6]);
-    bfly4<DIR>(v[1], v[3], v[5], v[7]);
     const cx<R> e0 = v[0], e1 = v[2], e2 = v[4], e3 = v[6];
     const cx<R> o0 = v[1], o2 = v[5];
     const cx<R> u1 = w8_1_unscaled<DIR>(v[3]);       // O[1] W8   =  h u1
@@ -313,9 +423,56 @@ template <int DIR, typename R> MDSP_HD void bfly8(cx<R> (&v)[8]) {
     v[3] = caxmy_k(h, u3, e3);
     v[7] = caxpy_k(h, u3, e3);
 }
+template <int DIR, typename R> MDSP_HD void bfly8(cx<R> (&v)[8]) {
+    // even / odd radix-4 sub-transforms: E[k] lands in v[2k], O[k] in v[2k+1]
+    bfly4<DIR>(v[0], v[2], v[4], v[6]);
+    bfly4<DIR>(v[1], v[3], v[5], v[7]);
+    bfly8_tail<DIR>(v);
+}
+
+// The folded radix-4 butterflies, scalar forms (Float64, the host, builds without the packed forms; the packed Float32 statements above do the
+// same operations in the same order).  bfly4_tw: a2 and a3 still lack their twiddles w2, w3 (conjugated for WDIR > 0).
+template <int DIR, int WDIR, typename R> MDSP_HD void bfly4_tw(cx<R>& a0, cx<R>& a1, cx<R>& a2, cx<R>& a3, cx<R> w2, cx<R> w3) {
+    const cx2<R> e = fold<WDIR>(a0, a2, w2), o = fold<WDIR>(a1, a3, w3);
+    a0 = cadd(e.plus, o.plus);
+    a2 = csub(e.plus, o.plus);
+    a1 = add_mi<DIR>(e.minus, o.minus);
+    a3 = sub_mi<DIR>(e.minus, o.minus);
+}
+// bfly4_w16: column Q = 1..3 of the radix-16 butterfly's outer stage, a_m still lacking W16^{mQ}.  The product of a1 is formed (it is the FIRST
+// operand of its pair), those of a2 and a3 fold.
+template <int DIR, int Q, typename R> MDSP_HD void bfly4_w16(cx<R>& a0, cx<R>& a1, cx<R>& a2, cx<R>& a3) {
+    constexpr R c1 = (R)0.92387953251128675612818318939679L, s1 = (R)0.38268343236508977172845998403040L, h = (R)0.70710678118654752440084436210485L;
+    const cx<R> w1 = {c1, -s1}, w3 = {s1, -c1}, w9 = {-c1, s1};
+    cx2<R> e, o;
+    if constexpr (Q == 1) {
+        const cx<R> p = twmul_k<DIR>(a1, w1);
+        e = fold_re(a0, h, w8_1_unscaled<DIR>(a2));
+        o = fold<DIR>(p, a3, w3);
+    } else if constexpr (Q == 2) {
+        const cx<R> p = cscale_k(h, w8_1_unscaled<DIR>(a1));
+        e = fold_mi<DIR>(a0, a2);
+        o = fold_re(p, -h, w8_3_unscaled_neg<DIR>(a3));
+    } else {
+        const cx<R> p = twmul_k<DIR>(a1, w3);
+        e = fold_re(a0, -h, w8_3_unscaled_neg<DIR>(a2));
+        o = fold<DIR>(p, a3, w9);
+    }
+    a0 = cadd(e.plus, o.plus);
+    a2 = csub(e.plus, o.plus);
+    a1 = add_mi<DIR>(e.minus, o.minus);
+    a3 = sub_mi<DIR>(e.minus, o.minus);
+}
 
 // everything of the radix-16 butterfly after the four inner DFT4s: v[m + 4q] = y[m][q] in, natural order out
-template <int DIR, typename R> MDSP_HD void bfly16_tail(cx<R> (&v)[16]) {
+// FOLD: the products of the outer stage's second operands ride in its add / subtract pairs (bfly4_w16), 6 operations less
+template <int DIR, bool FOLD = false, typename R> MDSP_HD void bfly16_tail(cx<R> (&v)[16]) {
+    if constexpr (FOLD) {
+        bfly4<DIR>(v[0], v[1], v[2], v[3]);
+        bfly4_w16<DIR, 1>(v[4], v[5], v[6], v[7]);
+        bfly4_w16<DIR, 2>(v[8], v[9], v[10], v[11]);
+        bfly4_w16<DIR, 3>(v[12], v[13], v[14], v[15]);
+    } else {
     constexpr R c1 = (R)0.92387953251128675612818318939679L;  // cos(pi/8)
     constexpr R s1 = (R)0.38268343236508977172845998403040L;  // sin(pi/8)
     constexpr R h = (R)0.70710678118654752440084436210485L;
@@ -333,6 +490,7 @@ template <int DIR, typename R> MDSP_HD void bfly16_tail(cx<R> (&v)[16]) {
     // outer DFT4 over m for each q; result p lands in slot m=p of the same group: X[4p+q] in v[p + 4q]
 #pragma unroll
     for (int q = 0; q < 4; ++q) bfly4<DIR>(v[4 * q + 0], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+    }
     // reorder v[p + 4q] -> natural index 4p + q  (a 4x4 transpose of register names; free after unrolling)
     cx<R> t;
 #define MDSP_SWAP(a, b) \
@@ -343,11 +501,11 @@ template <int DIR, typename R> MDSP_HD void bfly16_tail(cx<R> (&v)[16]) {
 #undef MDSP_SWAP
 }
 
-template <int DIR, typename R> MDSP_HD void bfly16(cx<R> (&v)[16]) {
+template <int DIR, bool FOLD = false, typename R> MDSP_HD void bfly16(cx<R> (&v)[16]) {
     // n = m + 4 s, k = 4 p + q :  X[4p+q] = sum_m W4^{mp} W16^{mq} ( sum_s v[m+4s] W4^{sq} )
 #pragma unroll
     for (int m = 0; m < 4; ++m) bfly4<DIR>(v[m], v[m + 4], v[m + 8], v[m + 12]);  // y[m][q] in v[m + 4q]
-    bfly16_tail<DIR>(v);
+    bfly16_tail<DIR, FOLD>(v);
 }
 
 // The same butterfly on WINDOWED input with the window folded into the first add/subtract stage:
@@ -389,6 +547,37 @@ template <int DIR, int RDX, typename R> MDSP_HD void twmul_all(cx<R> (&v)[RDX], 
 #pragma unroll
     for (int r = 1; r < RDX; ++r) v[r] = twmul<DIR>(v[r], w[r]);
 }
+
+// twmul_all followed by the butterfly, up to the fused roundings, with the products of the first stage's SECOND operands (v[8..15] / v[4..7])
+// folded into it: 8 of 15 (4 of 7) products become folds.  The first operands are multiplied as twmul_all does.  WDIR: direction of the
+// twiddles (w conjugated for WDIR > 0); W0: v[0] has a factor w[0] too.
+template <int WDIR, int RDX, bool W0, typename R> MDSP_HD void twmul_first(cx<R> (&v)[RDX], const cx<R> (&w)[RDX]) {
+    constexpr int HALF = RDX / 2, R0 = W0 ? 0 : 1;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(MDSP_NO_PACKED_F32) && MDSP_PK_FUSED
+    if constexpr (sizeof(R) == 4) {
+#pragma unroll
+        for (int r = R0; r + 1 < HALF; r += 2) cmul2(v[r], w[r], v[r + 1], w[r + 1], WDIR > 0);
+        if constexpr (((HALF - R0) & 1) != 0) v[HALF - 1] = twmul<WDIR>(v[HALF - 1], w[HALF - 1]);
+        return;
+    }
+#endif
+#pragma unroll
+    for (int r = R0; r < HALF; ++r) v[r] = twmul<WDIR>(v[r], w[r]);
+}
+template <int DIR, int WDIR = DIR, bool W0 = false, typename R> MDSP_HD void bfly16_tw(cx<R> (&v)[16], const cx<R> (&w)[16]) {
+    twmul_first<WDIR, 16, W0>(v, w);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) bfly4_tw<DIR, WDIR>(v[m], v[m + 4], v[m + 8], v[m + 12], w[m + 8], w[m + 12]);
+    bfly16_tail<DIR, true>(v);
+}
+template <int DIR, typename R> MDSP_HD void bfly8_tw(cx<R> (&v)[8], const cx<R> (&w)[8]) {
+    twmul_first<DIR, 8, false>(v, w);
+    bfly4_tw<DIR, DIR>(v[0], v[2], v[4], v[6], w[4], w[6]);
+    bfly4_tw<DIR, DIR>(v[1], v[3], v[5], v[7], w[5], w[7]);
+    bfly8_tail<DIR>(v);
+}
+// The inverse's first butterfly on a spectrum that still lacks its filter factor: DFT16 of v[e] H[e] (H not conjugated), e >= 8 folded
+template <int DIR, typename R> MDSP_HD void bfly16_h(cx<R> (&v)[16], const cx<R> (&H)[16]) { bfly16_tw<DIR, -1, true>(v, H); }
 
 // ------------------------------------------------------------------------------------------------ configuration
 // N points, E elements per thread (power of two, 4..16), T = N/E threads per transform.
@@ -486,10 +675,12 @@ MDSP_HD void load_twiddles(cx<R> (&tw)[C::NTW > 0 ? C::NTW : 1], int t, const cx
 
 // One Stockham pass on the thread's registers.  Non-final passes scatter their results to `lds`
 // (this transform's region); the final pass leaves X[t + T*e] in x[e].
-template <typename C, int DIR, int PASS, int TWMODE, int PADSHIFT, typename R>
+// FOLD: radix-16 and radix-8 passes take the folded butterflies (bfly16_tw / bfly8_tw, bfly16_tail<DIR, true>): fewer operations, fused roundings.
+template <typename C, int DIR, int PASS, int TWMODE, int PADSHIFT, bool FOLD = false, typename R>
 MDSP_HD void pass_compute(cx<R> (&x)[C::E], int t, const cx<R> (&tw)[C::NTW > 0 ? C::NTW : 1], const cx<R>* table, cx<R>* lds) {
     constexpr int Rdx = C::radix(PASS), NB = C::E / Rdx, Ns = C::ns(PASS);
     constexpr bool LAST = PASS == C::P - 1;
+    constexpr bool FOLDED_TW = FOLD && PASS > 0 && (Rdx == 16 || Rdx == 8);   // twiddles and butterfly in one call
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         cx<R> v[Rdx];
@@ -510,9 +701,14 @@ MDSP_HD void pass_compute(cx<R> (&x)[C::E], int t, const cx<R> (&tw)[C::NTW > 0 
                     wv[r] = table[kt + (C::ldsoff(PASS) + (r - 1) * Ns + KB)];
                 } else wv[r] = table[tw_index<C, PASS>(t, b, r)];
             }
-            twmul_all<DIR, Rdx>(v, wv);
+            if constexpr (FOLDED_TW && Rdx == 16) bfly16_tw<DIR>(v, wv);
+            else if constexpr (FOLDED_TW) bfly8_tw<DIR>(v, wv);
+            else twmul_all<DIR, Rdx>(v, wv);
         }
-        bfly<Rdx, DIR>(v);
+        if constexpr (!FOLDED_TW) {
+            if constexpr (FOLD && Rdx == 16) bfly16<DIR, true>(v);
+            else bfly<Rdx, DIR>(v);
+        }
         if constexpr (LAST) {
 #pragma unroll
             for (int r = 0; r < Rdx; ++r) x[b + r * NB] = v[r];
@@ -537,6 +733,14 @@ MDSP_HD void pass0_windowed(const cx<R> (&q)[8], const cx<R> (&f)[8], const cx<R
     static_assert(C::E == 16 && C::radix(0) == 16 && C::P > 1, "E = 16 geometries with a radix-16 first pass");
     cx<R> v[16];
     bfly16_win<-1>(q, f, wp, v);
+    pass0_scatter<C, PADSHIFT>(v, t, lds);
+}
+
+// Pass 0 of an E = 16 transform of v[e] H[e] (the filter spectrum of overlap-save in front of the inverse transform): the product rides in the
+// butterfly's first stage (bfly16_h)
+template <typename C, int DIR, int PADSHIFT, typename R> MDSP_HD void pass0_spectrum(cx<R> (&v)[16], const cx<R> (&H)[16], int t, cx<R>* lds) {
+    static_assert(C::E == 16 && C::radix(0) == 16 && C::P > 1, "E = 16 geometries with a radix-16 first pass");
+    bfly16_h<DIR>(v, H);
     pass0_scatter<C, PADSHIFT>(v, t, lds);
 }
 

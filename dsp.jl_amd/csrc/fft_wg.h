@@ -27,11 +27,12 @@ template <int T> __device__ __forceinline__ void wg_sync() {
 template <typename C, int PADSHIFT, int NBUF> constexpr int wg_lds_elems() { return NBUF * lds_elems<C::N, PADSHIFT>(); }
 
 // XBASE: index (mod NBUF) of the buffer used by this transform's first exchange.
-template <typename C, int DIR, int TWMODE, int PADSHIFT, int NBUF, int XBASE, int PASS = 0, typename R>
+// FOLD: the folded butterflies (pass_compute).
+template <typename C, int DIR, int TWMODE, int PADSHIFT, int NBUF, int XBASE, int PASS = 0, bool FOLD = false, typename R>
 __device__ __forceinline__ void wg_fft(cx<R> (&v)[C::E], int t, const cx<R> (&tw)[C::NTW > 0 ? C::NTW : 1], const cx<R>* table, cx<R>* lds) {
     constexpr int BUF = (XBASE + PASS) % NBUF;
     cx<R>* region = lds + BUF * lds_elems<C::N, PADSHIFT>();
-    pass_compute<C, DIR, PASS, TWMODE, PADSHIFT>(v, t, tw, table, region);
+    pass_compute<C, DIR, PASS, TWMODE, PADSHIFT, FOLD>(v, t, tw, table, region);
     if constexpr (PASS < C::P - 1) {
 #if MDSP_FFT_SETPRIO
         __builtin_amdgcn_s_setprio(1);   // experiment: the exchange (latency chain: barrier, LDS reads) outranks the partner wave's butterflies
@@ -42,8 +43,18 @@ __device__ __forceinline__ void wg_fft(cx<R> (&v)[C::E], int t, const cx<R> (&tw
 #if MDSP_FFT_SETPRIO
         __builtin_amdgcn_s_setprio(0);
 #endif
-        wg_fft<C, DIR, TWMODE, PADSHIFT, NBUF, XBASE, PASS + 1>(v, t, tw, table, lds);
+        wg_fft<C, DIR, TWMODE, PADSHIFT, NBUF, XBASE, PASS + 1, FOLD>(v, t, tw, table, lds);
     }
+}
+
+// The folded transform of v[e] H[e] (single LDS buffer): pass 0 takes the factor H into its butterfly (pass0_spectrum), the rest is wg_fft.
+template <typename C, int DIR, int TWMODE, int PADSHIFT, typename R>
+__device__ __forceinline__ void wg_fft_spectrum(cx<R> (&v)[C::E], const cx<R> (&H)[C::E], int t, const cx<R> (&tw)[C::NTW > 0 ? C::NTW : 1], const cx<R>* table, cx<R>* lds) {
+    pass0_spectrum<C, DIR, PADSHIFT>(v, H, t, lds);
+    wg_sync<C::T>();
+    pass_reload<C, PADSHIFT>(v, t, lds);
+    wg_sync<C::T>();
+    wg_fft<C, DIR, TWMODE, PADSHIFT, 1, 0, 1, true>(v, t, tw, table, lds);
 }
 
 // Twiddle source setup for a kernel: registers (loaded once per persistent workgroup), an LDS-resident table shared

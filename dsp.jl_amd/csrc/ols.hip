@@ -189,9 +189,11 @@ __device__ __forceinline__ void ols_store(const cx<R> (&v)[E], const OlsFusedArg
     }
 }
 
-template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false>
+// FOLD: the folded butterflies (fft_lds.h: products that only feed an add / subtract pair ride in it), the spectrum product inside the inverse's pass 0
+template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false>
 __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs a) {
     static_assert(!ROWS || (CPLX && !HREG), "the rows form: complex blocks, one spectrum row per block");
+    static_assert(!FOLD || (HREG && NBUF == 1 && E == 16), "the folded form: spectrum in registers, one LDS buffer");
     using C = fft::Cfg<N, E>;
     constexpr int T = C::T, PADSHIFT = 4;
     static_assert(T % 64 == 0, "a transform must own whole wavefronts (uniform descriptors)");
@@ -237,8 +239,11 @@ __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs 
         // next unit's samples start streaming from HBM while this unit is transformed
         if constexpr (PREFETCH) { if (!MDSP_ABLATED(a, 1)) ols_issue_loads<R, E, T, CPLX>(raw, a, nxt, t); }
         if (!MDSP_ABLATED(a, 2)) {
-        fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0>(v, t, tw, twsrc, lds);
+        fft::wg_fft<C, -1, TWMODE, PADSHIFT, NBUF, 0, 0, FOLD>(v, t, tw, twsrc, lds);
         // spectral multiply (K2): natural order in registers
+        if constexpr (FOLD) {   // ... inside the inverse's first butterfly
+            fft::wg_fft_spectrum<C, +1, TWMODE, PADSHIFT>(v, Hr, t, tw, twsrc, lds);
+        } else {
         if constexpr (HREG) {
 #pragma unroll
             for (int e = 0; e < E; ++e) v[e] = fft::cmul(v[e], Hr[e]);
@@ -254,6 +259,7 @@ __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs 
         }
         // inverse transform (unnormalised, like plan_brfft / inv(p).p)
         fft::wg_fft<C, +1, TWMODE, PADSHIFT, NBUF, (C::P - 1) % NBUF>(v, t, tw, twsrc, lds);
+        }
         if constexpr (ROWS) {   // conj(W^{k1 (t + T e)}) = conj(W^{k1 t} W^{k1 T e}): one table walk per thread and row, E uniform ones (scalar loads)
             const cx<R>*t0 = static_cast<const cx<R>*>(a.rt0), *t1 = static_cast<const cx<R>*>(a.rt1);
             const unsigned k1 = (unsigned)(cur.p % a.hrows), mask = (1u << a.rlogS) - 1u;
@@ -743,9 +749,9 @@ template <typename R> int upload_table(DevBuf& buf, int64_t n) {
 }
 
 // ---- fused launch ---------------------------------------------------------------------------------------
-template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false>
+template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false>
 int launch_fused_geo(const OlsFusedArgs& a, hipStream_t s) {
-    auto kern = ols_fused_kernel<R, N, E, G, TWMODE, CPLX, NBUF, PREFETCH, HREG, ROWS>;
+    auto kern = ols_fused_kernel<R, N, E, G, TWMODE, CPLX, NBUF, PREFETCH, HREG, ROWS, FOLD>;
     constexpr int threads = (N / E) * G;
     int per_cu = 0;
     MDSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0));
@@ -809,13 +815,16 @@ template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a
     // 128-thread workgroup (191 VGPRs, four workgroups of two waves per CU) -- the two transforms of a 256-thread workgroup share every
     // s_barrier although they exchange nothing.  12-round interleaved A/B on two boxes (profiles/r02l_ols_decoupled.json, r02e_ols_ab.json):
     // 1.85 / 1.78 ms against 2.05 / 1.97 for the same kernel with two transforms per workgroup.
-    if constexpr (N == 2048 && !CPLX && !DBL) return launch_fused_geo<R, N, 16, 1, 1, CPLX, 1, false>(a, s);
+    // ... with the folded butterflies: 512 packed operations per unit instead of 576 (profiles/r08_ols_fold_ab.json).
+    if constexpr (N == 2048 && !CPLX && !DBL) return launch_fused_geo<R, N, 16, 1, 1, CPLX, 1, false, true, false, true>(a, s);
+    else {
     // Software prefetch of the next unit's samples: OFF by default.  Measured on MI355X (profiles/r02c_tune.json, 2^30 Float32, nfft 2048):
     // the same geometry without the prefetch is 14 % faster (1.85 vs 2.16 ms) -- the 32 registers it frees matter less than the issue
     // pattern: loads at the top of the iteration park the wave while its partner workgroup on the SIMD computes, which puts the two
     // resident workgroups in antiphase on their own.  MDSP_OLS_PREFETCH=1 restores the prefetching form (tools/bench_matrix.py sweeps both).
     if (tunables().ols_prefetch == 1) return launch_fused_geo<R, N, E, G, TWREG, CPLX, NBUF, true>(a, s);
     return launch_fused_geo<R, N, E, G, TWREG, CPLX, NBUF, false>(a, s);
+    }
 }
 
 template <typename R, bool CPLX> int launch_fused(int64_t nfft, const OlsFusedArgs& a, hipStream_t s) {
