@@ -125,6 +125,7 @@ static const KnobDef kKnobs[] = {
     {"MDSP_ARB_PRIO", &Tunables::arb_prio, 0, 0, 3},
     {"MDSP_ARB_TILE", &Tunables::arb_tile, 0, 0, 1 << 20},
     {"MDSP_OLS_PREFETCH", &Tunables::ols_prefetch, 0, 0, 1},
+    {"MDSP_OLS_TILE", &Tunables::ols_tile, 1, 0, 1},
     {"MDSP_GEN_WIDE", &Tunables::gen_wide, 1, 0, 1},
     {"MDSP_GEN_CT_F64_MAX", &Tunables::gen_ct_f64_max, 8000, 0, 1 << 20},
     {"MDSP_BIG_GROUPS", &Tunables::big_groups, 0, 0, 1 << 20},

@@ -166,6 +166,7 @@ struct Tunables {
     int fir_mm_nd = 0, fir_mm_ns = 0;   // MDSP_FIR_MM_ND / _NS     : its DMA / store waves (0 = default: 2 DMA waves, 2 store waves for ratios >= 1, else 4)
     int gen_wide = 1;                   // MDSP_GEN_WIDE=0          : nextfastfft sizes: round 3's schedules of small radices instead of the three-pass composite-radix ones
     int gen_ct_f64_max = 8000;          // MDSP_GEN_CT_F64_MAX      : Float64 nextfastfft sizes above this leave the single-workgroup compile-time schedules (for the multi-pass engine)
+    int ols_tile = 1;                   // MDSP_OLS_TILE=0          : no tiled overlap-save plans (ols_plan.h): every plan runs windows of L outputs with nb - 1 samples of lead
     int ols_prefetch = 0;               // MDSP_OLS_PREFETCH=1      : overlap-save kernel with software prefetch of the next unit (default: off)
     int gx = 1;                         // MDSP_GX=0|2              : 0 = no run-time-schedule single-workgroup kernel (spectral_gx.h: sizes without a compile-time schedule go to
                                         //                            the round-2 LDS kernel / the multi-pass engine / rocFFT as up to round 5); 2 = that kernel for EVERY size it plans (A/B); 6 = no rows above 8192 points (spectral_ctcols_big.hip); 4 = never the compile-time kernels of spectral_ctcols.hip / spectral_ctbig.hip, 5 = never spectral_ctbig.hip (A/B)

@@ -117,6 +117,24 @@ template <typename T, int E, int TT, int E0> __device__ __forceinline__ void loa
     for (int e = E0; e < E; ++e) out[e] = Ld<T>::load(r, off + TT * e * SZ);
 }
 
+// elements e = 0 .. E0-1 only (the head of a window that could not be taken from the previous one)
+template <typename T, int E, int TT, int E0> __device__ __forceinline__ void load_window_head(T (&out)[E], __amdgpu_buffer_rsrc_t r, int t) {
+    constexpr int SZ = (int)sizeof(T);
+    int off = t * SZ;
+    asm volatile("" : "+v"(off));
+#pragma unroll
+    for (int e = 0; e < E0; ++e) out[e] = Ld<T>::load(r, off + TT * e * SZ);
+}
+
+// Stores of elements E0 .. E-1 of a window whose dropped lead is exactly E0 whole elements (E0 TT samples): plain stores, no per-lane test
+template <typename T, int E, int TT, int E0, typename F> __device__ __forceinline__ void store_window_tail(F&& get, __amdgpu_buffer_rsrc_t w, int t) {
+    constexpr int SZ = (int)sizeof(T);
+    int off = t * SZ;
+    asm volatile("" : "+v"(off));
+#pragma unroll
+    for (int e = E0; e < E; ++e) Ld<T>::store(get(e), w, off + TT * e * SZ);
+}
+
 // Stores of elements ES .. E-1 of a window whose first `lead` elements are dropped, with ES = lead div TT known at compile time: elements above
 // ES are plain stores (one VGPR offset + immediates), element ES drops its lanes t < lead - ES TT through the OOB sentinel, elements below ES
 // issue nothing at all.

@@ -251,13 +251,14 @@ int mdsp_host_unregister(void* host_ptr) {
 }
 
 // filt / conv of host arrays: columns one after the other, each in runs of whole overlap-save blocks (an even number of them: two
-// real blocks share a transform).  Chunk c of a column computes blocks [g0, g1) of THE SAME block grid the device-resident call uses
-// (mdsp_ols_exec_range), from the samples [g0 L - (nb-1), g1 L) -- so host and device calls return bit-identical results.
+// real blocks share a transform).  Chunk c of a column computes tiles [g0, g1) of THE SAME grid the device-resident call runs
+// (mdsp::ols_exec_tiles; the plan's tiles are the public blocks except on tiled plans, ols_plan.h), from the samples [g0 L - lead, g1 L) -- so host
+// and device calls return bit-identical results.
 int mdsp_ols_exec_host(mdsp_ols_plan plan, const void* x_host, int64_t nx, int64_t ncols, int64_t ldx, void* y_host, int64_t nout, int64_t ldy,
                        int flags) {
     if (!plan) MDSP_FAIL(MDSP_ERR_ARGUMENT, "plan is NULL");
     if (nx < 0 || ncols < 0 || nout < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "negative size");
-    const int64_t L = plan->L, nb = plan->nb;
+    const int64_t L = plan->tile, lead = plan->tile_lead, nb = plan->nb;
     const int dtype = plan->dtype;
     if (nout > nx + nb - 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "nout (%lld) exceeds nx+nb-1", (long long)nout);
     if (ncols > 1 && (ldx < nx || ldy < nout)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "leading dimension smaller than the column length");
@@ -271,7 +272,7 @@ int mdsp_ols_exec_host(mdsp_ols_plan plan, const void* x_host, int64_t nx, int64
     int64_t bpc = std::max<int64_t>(4, ((int64_t)tunables().host_chunk_mib << 20) / (int64_t)(L * (int64_t)esz));
     bpc &= ~int64_t(3);   // a multiple of four blocks: the hand-allocated kernel's units (mdsp_ols_w64_asm) start at multiples of four, so a chunk and the
                           // whole column run every block through the same kernel and the results stay bit-identical
-    const size_t in_cap = (size_t)(bpc * L + nb - 1) * esz, out_cap = (size_t)(bpc * L) * esz;
+    const size_t in_cap = (size_t)(bpc * L + lead) * esz, out_cap = (size_t)(bpc * L) * esz;
 
     hostpipe::Session ss(in_cap, out_cap, pinned);
     int rc = ss.status();
@@ -282,11 +283,11 @@ int mdsp_ols_exec_host(mdsp_ols_plan plan, const void* x_host, int64_t nx, int64
             hostpipe::Lane* ln = nullptr;
             if ((rc = ss.acquire(&ln)) != MDSP_OK) break;
             const int64_t g1 = std::min(nblocks, g0 + bpc);
-            const int64_t lo = std::max<int64_t>(0, g0 * L - (nb - 1)), hi = std::min(nx, g1 * L);
+            const int64_t lo = std::max<int64_t>(0, g0 * L - lead), hi = std::min(nx, g1 * L);
             const int64_t o0 = g0 * L, o1 = std::min(nout, g1 * L);
             const size_t inb = hi > lo ? (size_t)(hi - lo) * esz : 0, outb = (size_t)(o1 - o0) * esz;
             if ((rc = ss.upload(ln, xc + (size_t)lo * esz, inb, inb, 1)) != MDSP_OK) break;
-            rc = mdsp_ols_exec_range(plan, ln->din.p, lo, hi > lo ? hi - lo : 0, nx, ln->dout.p, g0, g1 - g0, nout, ss.kstream());
+            rc = mdsp::ols_exec_tiles(plan, ln->din.p, lo, hi > lo ? hi - lo : 0, nx, ln->dout.p, g0, g1 - g0, nout, ss.kstream());
             if (rc != MDSP_OK) break;
             rc = ss.download(ln, yc + (size_t)o0 * esz, outb, outb, 1, 0, outb);
         }

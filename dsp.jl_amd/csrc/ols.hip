@@ -100,6 +100,7 @@ struct OlsFusedArgs {
     int64_t nunits;         // total (one past the last unit of this launch)
     int64_t u_begin;        // first unit of this launch (0 unless a block range is executed, mdsp_ols_exec_range)
     int nb;
+    int lead;               // samples a window starts in front of its first output, all dropped on the way out: nb - 1, or the tile lead of a tiled plan (ols_plan.h)
     int64_t run_len;        // a slot takes runs of run_len consecutive units ...
     int64_t niter;          // ... runs_per_slot * run_len iterations in total (same for every slot)
     int ablate;             // profiling aid, -DMDSP_DEBUG_KNOBS builds only (MDSP_ABLATE): 1 skip HBM loads, 2 skip transforms, 4 skip stores
@@ -155,7 +156,7 @@ __device__ __forceinline__ void ols_issue_loads(OlsRaw<R, E, CPLX>& raw, const O
     constexpr int64_t SZ = (int64_t)sizeof(TT);
     const TT* xc = static_cast<const TT*>(a.x) + q.col * a.ldx;
     const int64_t g0 = CPLX ? q.p : 2 * q.p;      // first block of the unit
-    const int64_t start = g0 * a.L - (a.nb - 1);  // window start in x; negative for the leading blocks
+    const int64_t start = g0 * a.L - a.lead;      // window start in x; negative for the leading blocks
     {
         const __amdgpu_buffer_rsrc_t r = io::make_rsrc(xc + start, q.live ? (a.nx - start) * SZ : 0);
         const int lead = __builtin_amdgcn_readfirstlane((int)(start < 0 ? -start : 0));
@@ -170,13 +171,50 @@ __device__ __forceinline__ void ols_issue_loads(OlsRaw<R, E, CPLX>& raw, const O
     }
 }
 
-template <typename R, int E, int T, bool CPLX>
+// The tiled form (ols_plan.h: windows of E - K whole elements, K T samples of lead): block b of a unit starts (E - K) T samples behind block a, so
+// b[t + T e], e < K, IS a[t + T (E - K + e)] -- and the first K elements of the NEXT consecutive unit's block a are this unit's b[E - K .. E), still
+// in raw.b when that unit is loaded (`cont`, wave-uniform: same column, next pair, this unit had its second block).  Every sample is requested
+// once, and every window starts K T samples in front of a multiple of (E - K) T: on a 128-byte line when the column does.
+template <typename R, int E, int T, int K>
+__device__ __forceinline__ void ols_issue_loads_tiled(OlsRaw<R, E, false>& raw, const OlsFusedArgs& a, OlsPos q, bool cont, int t) {
+    constexpr int64_t SZ = (int64_t)sizeof(R);
+    const R* xc = static_cast<const R*>(a.x) + q.col * a.ldx;
+    const int64_t g0 = 2 * q.p;
+    const int64_t start = g0 * a.L - K * T;       // -K T for the first window of a column: its lead is zero padding, elements K .. E-1 start at x[0]
+    const bool haveB = q.live && (g0 + 1) < a.nblocks;
+    const __amdgpu_buffer_rsrc_t ra = io::make_rsrc(xc + start, q.live ? (a.nx - start) * SZ : 0);
+    if (cont) {
+#pragma unroll
+        for (int e = 0; e < K; ++e) raw.a[e] = raw.b[E - K + e];
+    } else if (start < 0) {
+#pragma unroll
+        for (int e = 0; e < K; ++e) raw.a[e] = (R)0;
+    } else {
+        io::load_window_head<R, E, T, K>(raw.a, ra, t);
+    }
+    io::load_window_tail<R, E, T, K>(raw.a, ra, t);
+    const int64_t startB = start + a.L;
+    const __amdgpu_buffer_rsrc_t rb = io::make_rsrc(xc + startB, haveB ? (a.nx - startB) * SZ : 0);
+    io::load_window_tail<R, E, T, K>(raw.b, rb, t);
+#pragma unroll
+    for (int e = 0; e < K; ++e) raw.b[e] = haveB ? raw.a[E - K + e] : (R)0;   // no second block: zeros, as its descriptor of no bytes returns them
+}
+
+template <typename R, int E, int T, bool CPLX, int KT = -1>
 __device__ __forceinline__ void ols_store(const cx<R> (&v)[E], const OlsFusedArgs& a, OlsPos q, int t) {
     using TT = std::conditional_t<CPLX, cx<R>, R>;
     constexpr int64_t SZ = (int64_t)sizeof(TT);
     const int64_t off0 = (CPLX ? q.p : 2 * q.p) * a.L;  // first output of the unit
-    const int lead = a.nb - 1;                          // K3: the first nb-1 samples of a block are aliased -> dropped
+    const int lead = KT >= 0 ? KT * T : a.lead;         // K3: the first nb-1 samples of a block are aliased -> dropped (tiled: KT whole elements)
     TT* yc = static_cast<TT*>(a.y) + q.col * a.ldy;
+    if constexpr (KT >= 0) {                            // elements KT .. E-1 of both windows: plain stores, nothing straddles
+        const __amdgpu_buffer_rsrc_t w = io::make_rsrc(yc + off0 - lead, q.live ? (a.nout - off0 + lead) * SZ : 0);
+        io::store_window_tail<TT, E, T, KT>([&](int e) { return v[e].x; }, w, t);
+        const int64_t offB = off0 + a.L;
+        const __amdgpu_buffer_rsrc_t wb = io::make_rsrc(yc + offB - lead, (q.live && offB < a.nout) ? (a.nout - offB + lead) * SZ : 0);
+        io::store_window_tail<TT, E, T, KT>([&](int e) { return v[e].y; }, wb, t);
+        return;
+    }
     {
         const __amdgpu_buffer_rsrc_t w = io::make_rsrc(yc + off0 - lead, q.live ? (a.nout - off0 + lead) * SZ : 0);
         if constexpr (CPLX) io::store_window<TT, E, T>([&](int e) { return v[e]; }, w, lead, t);
@@ -190,10 +228,13 @@ __device__ __forceinline__ void ols_store(const cx<R> (&v)[E], const OlsFusedArg
 }
 
 // FOLD: the folded butterflies (fft_lds.h: products that only feed an add / subtract pair ride in it), the spectrum product inside the inverse's pass 0
-template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false>
+// TILED: windows of E - K whole elements with a lead of K = 2 (ols_issue_loads_tiled); a.lead == K T, a.L == (E - K) T
+template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false, bool TILED = false>
 __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs a) {
     static_assert(!ROWS || (CPLX && !HREG), "the rows form: complex blocks, one spectrum row per block");
     static_assert(!FOLD || (HREG && NBUF == 1 && E == 16), "the folded form: spectrum in registers, one LDS buffer");
+    static_assert(!TILED || (FOLD && !CPLX && !PREFETCH && E == 16), "the tiled form: the folded kernel of real blocks, loads at the top of the iteration");
+    constexpr int K = 2;   // TILED: elements of lead
     using C = fft::Cfg<N, E>;
     constexpr int T = C::T, PADSHIFT = 4;
     static_assert(T % 64 == 0, "a transform must own whole wavefronts (uniform descriptors)");
@@ -220,12 +261,20 @@ __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs 
     OlsPos cur = ols_pos(a, walk, a.niter > 0);
     OlsRaw<R, E, CPLX> raw;
     if constexpr (PREFETCH) ols_issue_loads<R, E, T, CPLX>(raw, a, cur, t);
+    [[maybe_unused]] int64_t held_col = -1, held_p = -1;   // TILED: the unit whose second block's last K elements are still in raw.b (-1: none)
     for (int64_t it = 0; it < a.niter; ++it) {   // same trip count for every slot (barriers inside)
         ols_walk_next(walk, a.run_len, nslots);
         const OlsPos nxt = ols_pos(a, walk, it + 1 < a.niter);
         if constexpr (!PREFETCH) {
             if (!MDSP_ABLATED(a, 1)) {
                 if (a.memprio & 1) __builtin_amdgcn_s_setprio(3);
+                if constexpr (TILED) {
+                    const bool cont = cur.live && cur.col == held_col && cur.p == held_p + 1;
+                    ols_issue_loads_tiled<R, E, T, K>(raw, a, cur, cont, t);
+                    const bool haveB = cur.live && (2 * cur.p + 1) < a.nblocks;
+                    held_col = haveB ? cur.col : -1;
+                    held_p = cur.p;
+                } else
                 ols_issue_loads<R, E, T, CPLX>(raw, a, cur, t);
                 if (a.memprio & 1) __builtin_amdgcn_s_setprio(0);
             }
@@ -276,7 +325,7 @@ __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs 
         // exchanges of a unit alternate buffers so the next unit's first write is two barriers behind its readers
         if (!MDSP_ABLATED(a, 4)) {
             if (a.memprio & 2) __builtin_amdgcn_s_setprio(3);
-            ols_store<R, E, T, CPLX>(v, a, cur, t);
+            ols_store<R, E, T, CPLX, TILED ? K : -1>(v, a, cur, t);
             if (a.memprio & 2) __builtin_amdgcn_s_setprio(0);
         }
         cur = nxt;
@@ -749,9 +798,9 @@ template <typename R> int upload_table(DevBuf& buf, int64_t n) {
 }
 
 // ---- fused launch ---------------------------------------------------------------------------------------
-template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false>
+template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false, bool TILED = false>
 int launch_fused_geo(const OlsFusedArgs& a, hipStream_t s) {
-    auto kern = ols_fused_kernel<R, N, E, G, TWMODE, CPLX, NBUF, PREFETCH, HREG, ROWS, FOLD>;
+    auto kern = ols_fused_kernel<R, N, E, G, TWMODE, CPLX, NBUF, PREFETCH, HREG, ROWS, FOLD, TILED>;
     constexpr int threads = (N / E) * G;
     int per_cu = 0;
     MDSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0));
@@ -782,6 +831,7 @@ int ols_rows_impl(int dbl, void* work, int64_t rows, int hrows, const void* Hrow
     a.nx = a.nout = a.ldx = a.ldy = rows * S;
     a.L = S;
     a.nb = 1;
+    a.lead = 0;
     a.nblocks = a.units_per_col = a.nunits = rows;
     a.u_begin = 0;
     a.memprio = tunables().ols_prio;
@@ -794,7 +844,7 @@ int ols_rows_impl(int dbl, void* work, int64_t rows, int hrows, const void* Hrow
     return launch_fused_geo<float, 8192, 16, 1, 1, true, 1, false, false, true>(a, st);
 }
 
-template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a, hipStream_t s) {
+template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a, hipStream_t s, bool tiled) {
     // Geometry: E elements per thread so that a transform owns whole wavefronts (T = N/E >= 64); G transforms
     // per workgroup so that workgroups have 256 threads where possible.
     constexpr bool DBL = sizeof(R) == 8;
@@ -816,8 +866,15 @@ template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a
     // s_barrier although they exchange nothing.  12-round interleaved A/B on two boxes (profiles/r02l_ols_decoupled.json, r02e_ols_ab.json):
     // 1.85 / 1.78 ms against 2.05 / 1.97 for the same kernel with two transforms per workgroup.
     // ... with the folded butterflies: 512 packed operations per unit instead of 576 (profiles/r08_ols_fold_ab.json).
-    if constexpr (N == 2048 && !CPLX && !DBL) return launch_fused_geo<R, N, 16, 1, 1, CPLX, 1, false, true, false, true>(a, s);
-    else {
+    // ... and, for plans the tile rule admits (ols_plan.h), windows that start on cache lines and the block overlap kept in registers.
+    if constexpr (N == 2048 && !CPLX && !DBL) {
+        if (tiled) {
+            if (a.lead != 2 * 128 || a.L != 14 * 128) MDSP_FAIL(MDSP_ERR_ASSERTION, "tiled overlap-save launch with tile %lld, lead %d", (long long)a.L, a.lead);
+            return launch_fused_geo<R, N, 16, 1, 1, CPLX, 1, false, true, false, true, true>(a, s);
+        }
+        return launch_fused_geo<R, N, 16, 1, 1, CPLX, 1, false, true, false, true>(a, s);
+    } else {
+    if (tiled) MDSP_FAIL(MDSP_ERR_ASSERTION, "no tiled overlap-save kernel for nfft=%d", N);
     // Software prefetch of the next unit's samples: OFF by default.  Measured on MI355X (profiles/r02c_tune.json, 2^30 Float32, nfft 2048):
     // the same geometry without the prefetch is 14 % faster (1.85 vs 2.16 ms) -- the 32 registers it frees matter less than the issue
     // pattern: loads at the top of the iteration park the wave while its partner workgroup on the SIMD computes, which puts the two
@@ -827,15 +884,15 @@ template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a
     }
 }
 
-template <typename R, bool CPLX> int launch_fused(int64_t nfft, const OlsFusedArgs& a, hipStream_t s) {
+template <typename R, bool CPLX> int launch_fused(int64_t nfft, const OlsFusedArgs& a, hipStream_t s, bool tiled = false) {
     switch (nfft) {
-        case 256: return launch_fused_n<R, 256, CPLX>(a, s);
-        case 512: return launch_fused_n<R, 512, CPLX>(a, s);
-        case 1024: return launch_fused_n<R, 1024, CPLX>(a, s);
-        case 2048: return launch_fused_n<R, 2048, CPLX>(a, s);
-        case 4096: return launch_fused_n<R, 4096, CPLX>(a, s);
+        case 256: return launch_fused_n<R, 256, CPLX>(a, s, tiled);
+        case 512: return launch_fused_n<R, 512, CPLX>(a, s, tiled);
+        case 1024: return launch_fused_n<R, 1024, CPLX>(a, s, tiled);
+        case 2048: return launch_fused_n<R, 2048, CPLX>(a, s, tiled);
+        case 4096: return launch_fused_n<R, 4096, CPLX>(a, s, tiled);
         case 8192:
-            if constexpr (sizeof(R) == 4) return launch_fused_n<R, 8192, CPLX>(a, s);
+            if constexpr (sizeof(R) == 4) return launch_fused_n<R, 8192, CPLX>(a, s, tiled);
         default: break;
     }
     MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "fused overlap-save does not support nfft=%lld", (long long)nfft);
@@ -1048,6 +1105,30 @@ static int ols_choose(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int 
     return MDSP_OK;
 }
 
+// The tile rule (ols_plan.h): real Float32, one partition, the fused engine's nfft 2048 kernel, a filter that leaves at most kTilePMax of the
+// 256 lead samples unused -- a tile shorter than L by p = 256 - (nb - 1) samples costs p / L more windows, and the tiled kernel's measured gain at p = 1
+// (1.7 % of the filter stage, profiles/ols_tile_ab.json) is spent to no more than half by p = 8.
+constexpr int64_t kTileNfft = 2048, kTileLead = 256, kTilePMax = 8;
+static bool ols_tile_rule(const OlsChoice& c, int64_t nb, int dtype, int64_t* tile, int64_t* lead) {
+    *tile = c.parts > 1 ? c.exec_nfft / 2 : c.exec_nfft - (nb - 1);
+    *lead = nb - 1;
+    if (tunables().ols_tile != 1 || c.eng != MDSP_ENGINE_FUSED || c.parts != 1 || c.big || dtype != MDSP_F32 || c.exec_nfft != kTileNfft) return false;
+    if (nb - 1 <= kTileLead / 2 || nb - 1 > kTileLead || kTileLead - (nb - 1) > kTilePMax) return false;
+    *tile = kTileNfft - kTileLead;
+    *lead = kTileLead;
+    return true;
+}
+
+int mdsp_ols_tile_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int mode, int engine, int64_t* tile_len, int64_t* tile_lead) {
+    OlsChoice c;
+    MDSP_TRY(ols_choose(nb, nfft, nx_hint, dtype, mode, engine, &c));
+    int64_t tile = 0, lead = 0;
+    (void)ols_tile_rule(c, nb, dtype, &tile, &lead);
+    if (tile_len) *tile_len = tile;
+    if (tile_lead) *tile_lead = lead;
+    return MDSP_OK;
+}
+
 int mdsp_ols_geometry_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int mode, int engine, int64_t* exec_nfft, int64_t* exec_block_len, int* partitions,
                           int* engine_used, int* rows) {
     OlsChoice c;
@@ -1083,6 +1164,7 @@ int mdsp_ols_plan_create(mdsp_ols_plan* plan, const void* taps_host, int64_t nb,
     pl->L = parts > 1 ? exec_nfft / 2 : exec_nfft - (nb - 1);
     pl->variant = tunables().ols_variant;
     pl->big = ch.big;
+    pl->tiled = ols_tile_rule(ch, nb, dtype, &pl->tile, &pl->tile_lead);
     nfft = exec_nfft;   // from here on: the transform size that executes
 
     // Filter spectrum in double on the host.  FILT: taps scaled by 1/nfft before the transform (filt.jl:499);
@@ -1185,15 +1267,24 @@ int mdsp_ols_plan_geometry(mdsp_ols_plan plan, int64_t* exec_nfft, int64_t* exec
     return MDSP_OK;
 }
 
+int mdsp_ols_plan_tile(mdsp_ols_plan plan, int64_t* tile_len, int64_t* tile_lead) {
+    if (!plan) MDSP_FAIL(MDSP_ERR_ARGUMENT, "plan is NULL");
+    if (tile_len) *tile_len = plan->tile;
+    if (tile_lead) *tile_lead = plan->tile_lead;
+    return MDSP_OK;
+}
+
 // (Round 4's hand-allocated kernel of the headline shape -- one wavefront per four blocks, csrc/ols_w64_asm.s -- measured 5 - 7 % SLOWER than ols_fused_kernel on
 // two boxes (profiles/r04_ols_asm_ablation.json) and was removed in round 5 together with its generator; HISTORY.md section 4.2 has the record.)
 
 // blocks [g_begin, g_end) of every column's block grid (g_end < 0: all).  x / y may be "virtual" bases: only the elements those blocks
-// touch are dereferenced (mdsp_ols_exec_range).
+// touch are dereferenced (mdsp_ols_exec_range).  tile_grid: the grid is the plan's tiles (the whole-column call, ols_exec_tiles) instead of the
+// public blocks of L outputs (mdsp_ols_exec_range); the two differ on tiled plans only.
 static int ols_exec_core(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx, void* y_dev, int64_t nout, int64_t ldy,
-                         int64_t g_begin, int64_t g_end, hipStream_t s, int64_t x_lo = 0) {
+                         int64_t g_begin, int64_t g_end, hipStream_t s, int64_t x_lo, bool tile_grid) {
     const bool cplx = dtype_is_complex(plan->dtype), dbl = dtype_is_double(plan->dtype);
-    const int64_t nblocks = cdiv(nout, plan->L);
+    const int64_t Lg = tile_grid ? plan->tile : plan->L;
+    const int64_t nblocks = cdiv(nout, Lg);
     if (plan->partitions > 1) {   // long filters: uniformly partitioned overlap-save
         if (ncols > 65535) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "more than 65535 columns per call");
         if (g_end < 0 || g_end > nblocks) g_end = nblocks;
@@ -1227,8 +1318,9 @@ static int ols_exec_core(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int6
     a.nout = nout;
     a.ldx = ldx;
     a.ldy = ldy;
-    a.L = plan->L;
+    a.L = Lg;
     a.nb = (int)plan->nb;
+    a.lead = (int)(tile_grid ? plan->tile_lead : plan->nb - 1);
     a.nblocks = g_end;                     // blocks past the range do not exist for this launch (second block of the last pair)
     a.units_per_col = cplx ? nblocks : cdiv(nblocks, 2);
     a.nunits = (g_end == nblocks) ? a.units_per_col * ncols : (cplx ? g_end : cdiv(g_end, 2));   // ranges: single column (checked by the caller)
@@ -1238,7 +1330,7 @@ static int ols_exec_core(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int6
     a.ablate = MDSP_DBG(ablate);
     a.memprio = tunables().ols_prio;
     if (cplx) return dbl ? launch_fused<double, true>(plan->nfft, a, s) : launch_fused<float, true>(plan->nfft, a, s);
-    return dbl ? launch_fused<double, false>(plan->nfft, a, s) : launch_fused<float, false>(plan->nfft, a, s);
+    return dbl ? launch_fused<double, false>(plan->nfft, a, s) : launch_fused<float, false>(plan->nfft, a, s, tile_grid && plan->tiled);
 }
 
 int mdsp_ols_exec(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx, void* y_dev, int64_t nout, int64_t ldy,
@@ -1251,20 +1343,21 @@ int mdsp_ols_exec(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t nco
     if (!x_dev && nx > 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "x is NULL");
     if (!y_dev) MDSP_FAIL(MDSP_ERR_ARGUMENT, "out is NULL");
     if (x_dev == y_dev) MDSP_FAIL(MDSP_ERR_ARGUMENT, "out may not alias x");
-    return ols_exec_core(plan, x_dev, nx, ncols, ldx, y_dev, nout, ldy, 0, -1, as_stream(stream));
+    return ols_exec_core(plan, x_dev, nx, ncols, ldx, y_dev, nout, ldy, 0, -1, as_stream(stream), 0, true);
 }
 
-int mdsp_ols_exec_range(mdsp_ols_plan plan, const void* xs_dev, int64_t xs_first, int64_t xs_len, int64_t nx, void* ys_dev, int64_t first_block,
-                        int64_t nblocks_range, int64_t nout, void* stream) {
+// a range of the public block grid (tile_grid false) or of the plan's tiles (true) from a slice of the signal
+static int ols_exec_slice(mdsp_ols_plan plan, const void* xs_dev, int64_t xs_first, int64_t xs_len, int64_t nx, void* ys_dev, int64_t first_block,
+                          int64_t nblocks_range, int64_t nout, hipStream_t stream, bool tile_grid) {
     if (!plan) MDSP_FAIL(MDSP_ERR_ARGUMENT, "plan is NULL");
     if (nx < 0 || nout < 0 || xs_first < 0 || xs_len < 0 || first_block < 0 || nblocks_range < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "negative size");
     if (nout > nx + plan->nb - 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "nout (%lld) exceeds nx+nb-1", (long long)nout);
-    const int64_t L = plan->L, nb = plan->nb, nblocks = cdiv(nout, L);
+    const int64_t L = tile_grid ? plan->tile : plan->L, lead = tile_grid ? plan->tile_lead : plan->nb - 1, nblocks = cdiv(nout, L);
     const int64_t g0 = first_block, g1 = std::min(nblocks, first_block + nblocks_range);
     if (g0 >= g1) return MDSP_OK;
     if (plan->partitions == 1 && !dtype_is_complex(plan->dtype) && (g0 & 1)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "first_block must be even (two real blocks share a transform)");
-    // samples the blocks read: [g0 L - (nb-1), g1 L) clipped to the signal
-    const int64_t need_lo = std::max<int64_t>(0, g0 * L - (nb - 1)), need_hi = std::min(nx, g1 * L);
+    // samples the blocks read: [g0 L - lead, g1 L) clipped to the signal
+    const int64_t need_lo = std::max<int64_t>(0, g0 * L - lead), need_hi = std::min(nx, g1 * L);
     if (need_hi > need_lo && (xs_first > need_lo || xs_first + xs_len < need_hi))
         MDSP_FAIL(MDSP_ERR_ARGUMENT, "the slice [%lld, %lld) does not cover the samples [%lld, %lld) that blocks [%lld, %lld) read", (long long)xs_first,
                   (long long)(xs_first + xs_len), (long long)need_lo, (long long)need_hi, (long long)g0, (long long)g1);
@@ -1278,7 +1371,12 @@ int mdsp_ols_exec_range(mdsp_ols_plan plan, const void* xs_dev, int64_t xs_first
     const int64_t nout_eff = std::min(nout, g1 * L);
     // partitioned plans warm their delay line up with the P blocks in front of g0: what the slice does not hold of them lies more than nb - 1
     // samples back, under the zero taps of the last partition, and is read as zero (x_lo)
-    return ols_exec_core(plan, xv, nx_eff, 1, nx_eff, yv, nout_eff, nout_eff, g0, g1, as_stream(stream), xs_first);
+    return ols_exec_core(plan, xv, nx_eff, 1, nx_eff, yv, nout_eff, nout_eff, g0, g1, stream, xs_first, tile_grid);
+}
+
+int mdsp_ols_exec_range(mdsp_ols_plan plan, const void* xs_dev, int64_t xs_first, int64_t xs_len, int64_t nx, void* ys_dev, int64_t first_block,
+                        int64_t nblocks_range, int64_t nout, void* stream) {
+    return ols_exec_slice(plan, xs_dev, xs_first, xs_len, nx, ys_dev, first_block, nblocks_range, nout, as_stream(stream), false);
 }
 
 int mdsp_ols_segment(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t first_block, int64_t nblocks, void* seg_dev, void* stream) {
@@ -1308,3 +1406,10 @@ int mdsp_ols_segment(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t 
 }
 
 }  // extern "C"
+
+namespace mdsp {
+int ols_exec_tiles(mdsp_ols_plan_s* plan, const void* xs_dev, int64_t xs_first, int64_t xs_len, int64_t nx, void* ys_dev, int64_t first_tile, int64_t ntiles,
+                   int64_t nout, hipStream_t stream) {
+    return ols_exec_slice(plan, xs_dev, xs_first, xs_len, nx, ys_dev, first_tile, ntiles, nout, stream, true);
+}
+}  // namespace mdsp

@@ -9,6 +9,12 @@ struct mdsp_ols_plan_s {
     int dtype = MDSP_F32, mode = MDSP_OLS_FILT, engine = MDSP_ENGINE_ROCFFT;
     int64_t nb = 0, nfft = 0, L = 0;      // nfft / L: the geometry that EXECUTES (== the reference's unless the fused engine re-blocked a long filter)
     int64_t ref_nfft = 0, ref_L = 0;     // what the caller / optimalfftfiltlength asked for (plan_info, mdsp_ols_segment: the reference's tmp1 blocks)
+    // What the whole-column call and the host pipeline execute: windows of `tile` outputs that start tile_lead samples in front of their first
+    // output.  Everywhere tile == L and tile_lead == nb - 1, except real Float32 plans of 249 .. 257 taps at nfft 2048 on the fused engine (`tiled`): 1792
+    // outputs per window and 256 samples of lead, so every window starts a multiple of 1 KiB into a line-aligned column and the overlap of consecutive
+    // blocks is whole per-thread elements.  The spectrum does not change (the taps past nb are zero either way); the public block grid (L) does not move.
+    int64_t tile = 0, tile_lead = 0;
+    bool tiled = false;
     int partitions = 1;                  // > 1: uniformly partitioned overlap-save (upols_fused_kernel): nfft = 2 B, `partitions` spectra in H
     mdsp::DevBuf H;       // rocFFT engine: nspec (real) or nfft (complex) entries; fused: nfft entries
     mdsp::DevBuf table;   // fused: nfft forward roots
@@ -22,3 +28,11 @@ struct mdsp_ols_plan_s {
     int big_rows = 0;                    // > 0: H is row-major for the rows form of that engine (R0 rows: bigfft.h ols_rows_r0)
     mdsp::big::EngineHolder bigeng;
 };
+
+namespace mdsp {
+// Tiles [first_tile, first_tile + ntiles) of the grid the whole-column call runs for one column of nx samples / nout outputs, from a slice of the signal:
+// xs_dev holds x[xs_first .. xs_first + xs_len) and covers [first_tile tile - tile_lead, (first_tile + ntiles) tile) clipped to [0, nx); ys_dev[0..] receives
+// the outputs from first_tile tile on.  first_tile even for real dtypes on single-block plans.  Bit-identical to the whole-column call (mdsp_ols_exec_host).
+int ols_exec_tiles(mdsp_ols_plan_s* plan, const void* xs_dev, int64_t xs_first, int64_t xs_len, int64_t nx, void* ys_dev, int64_t first_tile, int64_t ntiles,
+                   int64_t nout, hipStream_t stream);
+}  // namespace mdsp

@@ -129,6 +129,13 @@ int mdsp_ols_plan_geometry(mdsp_ols_plan plan, int64_t* exec_nfft, int64_t* exec
  * the rows form of the multi-pass engine (R0 rows of 8192 / 4096 points), else 0.  Any output pointer may be NULL. */
 int mdsp_ols_geometry_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int mode, int engine, int64_t* exec_nfft, int64_t* exec_block_len,
                           int* partitions, int* engine_used, int* rows);
+/* The windows mdsp_ols_exec and mdsp_ols_exec_host run: tile_len outputs each, starting tile_lead samples in front of their first output.
+ * Everywhere tile_len == exec_block_len and tile_lead == nb - 1, except on TILED plans -- real Float32, fused engine, exec_nfft 2048, 249 .. 257 taps:
+ * (1792, 256), so that every window starts a multiple of 1 KiB into the column and the overlap of neighbouring windows stays in registers.  The
+ * filter spectrum and the geometry the calls above report do not change; outputs agree with the untiled windows within rounding.  The knob
+ * MDSP_OLS_TILE = 0 (mdsp_set_knob, before the plan is made) switches the rule off.  mdsp_ols_tile_for: the same answer without a plan or a device. */
+int mdsp_ols_plan_tile(mdsp_ols_plan plan, int64_t* tile_len, int64_t* tile_lead);
+int mdsp_ols_tile_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int mode, int engine, int64_t* tile_len, int64_t* tile_lead);
 /* x_dev: (nx, ncols) ld ldx;  y_dev: (nout, ncols) ld ldy.  nout = nx (filt), nx+nb-1 (conv), or any
  * 0 <= nout <= nx+nb-1.  x and y must not alias (Filters/filt.jl:438-439). */
 int mdsp_ols_exec(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx, void* y_dev,
@@ -137,8 +144,9 @@ int mdsp_ols_exec(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t nco
  * nout outputs, from a slice of the signal: xs_dev holds x[xs_first .. xs_first + xs_len) and must cover the samples those blocks
  * read, [first_block L - (nb-1), (first_block + nblocks_range) L) clipped to [0, nx); ys_dev[0..] receives the outputs from
  * first_block L on (L = exec_block_len of mdsp_ols_plan_geometry).  first_block must be even for real dtypes on single-block plans
- * (bit-identical to the whole-column call); partitioned plans (long filters) take any first_block and agree with the whole-column call
- * within rounding.  Building block of mdsp_ols_exec_host and of a time-axis split
+ * (bit-identical to the whole-column call when mdsp_ols_plan_tile reports tile_len == exec_block_len, within rounding on tiled plans, whose
+ * block ranges run the untiled windows and never read in front of the slice); partitioned plans (long filters) take any first_block and agree
+ * with the whole-column call within rounding.  Building block of mdsp_ols_exec_host and of a time-axis split
  * of one stream over GPUs (no collective: overlap-save blocks are independent, Filters/filt.jl:504-518). */
 int mdsp_ols_exec_range(mdsp_ols_plan plan, const void* xs_dev, int64_t xs_first, int64_t xs_len, int64_t nx, void* ys_dev,
                         int64_t first_block, int64_t nblocks_range, int64_t nout, void* stream);

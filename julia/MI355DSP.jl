@@ -241,6 +241,18 @@ function ols_geometry_for(nb::Integer, nfft::Integer, nx::Integer, ::Type{T}, mo
                 nb, nfft, nx, mdtype(T), mode, engine, en, L, parts, eng, rows))
     (nfft = Int(en[]), L = Int(L[]), partitions = Int(parts[]), engine = Int(eng[]), rows = Int(rows[]))
 end
+# the windows the whole-column and host calls run: (tile, lead) == (L, nb - 1) except on tiled plans (real Float32, nfft 2048, 249 .. 257 taps: (1792, 256))
+function plan_tile(h::Ptr{Cvoid})
+    tile, lead = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_ols_plan_tile, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}), h, tile, lead))
+    (tile = Int(tile[]), lead = Int(lead[]))
+end
+function ols_tile_for(nb::Integer, nfft::Integer, nx::Integer, ::Type{T}, mode::Integer=OLS_FILT, engine::Integer=ENGINE_AUTO) where {T}
+    tile, lead = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_ols_tile_for, lib), Cint, (Int64, Int64, Int64, Cint, Cint, Cint, Ref{Int64}, Ref{Int64}),
+                nb, nfft, nx, mdtype(T), mode, engine, tile, lead))
+    (tile = Int(tile[]), lead = Int(lead[]))
+end
 
 # The function-style entry points build a plan per call in the reference (cheap FFTW plans); here the plan comes from the LIBRARY's LRU
 # (mdsp_ols_plan_cached: keyed by device, thread, stream and the contents of the taps) -- ~45 us per call instead of ~1 ms.  The handle is
