@@ -78,6 +78,7 @@ PROTOTYPES = {
     "mdsp_ols_exec": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
     "mdsp_ols_plan_tile": (ci, [vp, pi64, pi64]),
     "mdsp_ols_tile_for": (ci, [i64, i64, i64, ci, ci, ci, pi64, pi64]),
+    "mdsp_ols_stream_for": (ci, [i64, i64, i64, ci, pint]),
     "mdsp_ols_exec_range": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, i64, vp]),
     "mdsp_ols_exec_host": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, ci]),
     "mdsp_ols_segment": (ci, [vp, vp, i64, i64, i64, vp, vp]),
@@ -215,7 +216,7 @@ def lib() -> C.CDLL:
 ENV_VARIABLES = ("MDSP_ENGINE", "MDSP_WG_PER_CU", "MDSP_PLAN_CACHE_TOTAL", "MDSP_PLAN_CACHE_IDLE", "MDSP_ROCFFT_CHUNK_MIB", "MDSP_HOST_CHUNK_MIB", "MDSP_BIG_CHUNK_MIB",
                  "MDSP_BIGFFT", "MDSP_GX", "MDSP_FIR_MM", "MDSP_FIR_DEC", "MDSP_FIR_EXACT", "MDSP_ARB_SCAN", "MDSP_ARB_SCAN_MIN", "MDSP_FIR_CHOICE_FILE")
 _DEBUG_ENV = ("MDSP_ABLATE", "MDSP_WELCH_NOHALF", "MDSP_STFT_NOSHIFT", "MDSP_STFT_NOPAIR", "MDSP_STFT_NODIRECT", "MDSP_FIR_GENERIC", "MDSP_FIR_IDENTITY_LANES",
-              "MDSP_MT_PASSES", "MDSP_ARB_PROF")   # profiling switches of -DMDSP_DEBUG_KNOBS builds: environment only
+              "MDSP_MT_PASSES", "MDSP_ARB_PROF", "MDSP_OLS_AUX")   # profiling switches of -DMDSP_DEBUG_KNOBS builds: environment only
 
 
 def set_tunable(name: str, value) -> None:

@@ -126,6 +126,7 @@ static const KnobDef kKnobs[] = {
     {"MDSP_ARB_TILE", &Tunables::arb_tile, 0, 0, 1 << 20},
     {"MDSP_OLS_PREFETCH", &Tunables::ols_prefetch, 0, 0, 1},
     {"MDSP_OLS_TILE", &Tunables::ols_tile, 1, 0, 1},
+    {"MDSP_OLS_STREAM", &Tunables::ols_stream, 1, 0, 2},
     {"MDSP_GEN_WIDE", &Tunables::gen_wide, 1, 0, 1},
     {"MDSP_GEN_CT_F64_MAX", &Tunables::gen_ct_f64_max, 8000, 0, 1 << 20},
     {"MDSP_BIG_GROUPS", &Tunables::big_groups, 0, 0, 1 << 20},
@@ -196,6 +197,7 @@ static void read_tunables_locked() {
     for (const auto& o : knob_overrides()) t.*(kKnobs[o.first].field) = std::min(kKnobs[o.first].hi, std::max(kKnobs[o.first].lo, o.second));
 #ifdef MDSP_DEBUG_KNOBS
     t.ablate = geti("MDSP_ABLATE", 0);
+    t.ols_aux = geti("MDSP_OLS_AUX", -1);
     t.welch_nohalf = getenv("MDSP_WELCH_NOHALF") != nullptr;
     t.stft_noshift = getenv("MDSP_STFT_NOSHIFT") != nullptr;
     t.stft_nopair = getenv("MDSP_STFT_NOPAIR") != nullptr;

@@ -167,6 +167,8 @@ struct Tunables {
     int gen_wide = 1;                   // MDSP_GEN_WIDE=0          : nextfastfft sizes: round 3's schedules of small radices instead of the three-pass composite-radix ones
     int gen_ct_f64_max = 8000;          // MDSP_GEN_CT_F64_MAX      : Float64 nextfastfft sizes above this leave the single-workgroup compile-time schedules (for the multi-pass engine)
     int ols_tile = 1;                   // MDSP_OLS_TILE=0          : no tiled overlap-save plans (ols_plan.h): every plan runs windows of L outputs with nb - 1 samples of lead
+    int ols_stream = 1;                 // MDSP_OLS_STREAM=0|1|2    : streaming cache policy of the tiled overlap-save kernel (ols_plan.h ols_stream_rule), read at launch: 0 = never,
+                                        //                            1 = by the footprint rule (launches that touch more than 512 MiB; the default), 2 = every tiled launch (tests, A/B)
     int ols_prefetch = 0;               // MDSP_OLS_PREFETCH=1      : overlap-save kernel with software prefetch of the next unit (default: off)
     int gx = 1;                         // MDSP_GX=0|2              : 0 = no run-time-schedule single-workgroup kernel (spectral_gx.h: sizes without a compile-time schedule go to
                                         //                            the round-2 LDS kernel / the multi-pass engine / rocFFT as up to round 5); 2 = that kernel for EVERY size it plans (A/B); 6 = no rows above 8192 points (spectral_ctcols_big.hip); 4 = never the compile-time kernels of spectral_ctcols.hip / spectral_ctbig.hip, 5 = never spectral_ctbig.hip (A/B)
@@ -186,6 +188,7 @@ struct Tunables {
 #ifdef MDSP_DEBUG_KNOBS
     // Profiling / bisecting switches: only in builds made with -DMDSP_DEBUG_KNOBS (build.py --tag dbg --cflags -DMDSP_DEBUG_KNOBS).
     int ablate = 0;                     // MDSP_ABLATE: 1 skip HBM loads, 2 skip transforms, 4 skip stores / accumulation (results are garbage)
+    int ols_aux = -1;                   // MDSP_OLS_AUX: cache policy of the tiled overlap-save kernel, 100 loads + stores of the matrix in ols.hip (-1: what MDSP_OLS_STREAM says)
     bool welch_nohalf = false, stft_noshift = false, stft_nopair = false, stft_nodirect = false, fir_generic = false,
          fir_identity_lanes = false, mt_passes = false, arb_prof = false;
 #endif

@@ -19,7 +19,8 @@ using fft::cx;
 
 constexpr int OOB = (int)0x80000000;  // byte offset that is out of range for every descriptor built here
 
-// Cache policy (the `aux` immediate of the buffer instructions: bit 0 sc0, bit 1 nt, bit 4 sc1) of the streaming loads / stores.
+// Cache policy (the `aux` immediate of the buffer instructions: bit 0 sc0, bit 1 nt, bit 4 sc1) of the streaming loads / stores.  It is a template
+// parameter (AUX) of Ld<>::load / store and of the window helpers below, so a kernel instantiation chooses its own; these macros are its default.
 #ifndef MDSP_IO_AUX_LOAD
 #define MDSP_IO_AUX_LOAD 0
 #endif
@@ -38,52 +39,52 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, lo
 
 template <typename T> struct Ld;
 template <> struct Ld<float> {
-    static __device__ __forceinline__ float load(__amdgpu_buffer_rsrc_t r, int off) {
-        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, MDSP_IO_AUX_LOAD));
+    template <int AUX = MDSP_IO_AUX_LOAD> static __device__ __forceinline__ float load(__amdgpu_buffer_rsrc_t r, int off) {
+        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, AUX));
     }
-    static __device__ __forceinline__ void store(float v, __amdgpu_buffer_rsrc_t r, int off) {
-        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, off, 0, MDSP_IO_AUX_STORE);
+    template <int AUX = MDSP_IO_AUX_STORE> static __device__ __forceinline__ void store(float v, __amdgpu_buffer_rsrc_t r, int off) {
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, off, 0, AUX);
     }
 };
 template <> struct Ld<double> {
     typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ double load(__amdgpu_buffer_rsrc_t r, int off) {
-        const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, MDSP_IO_AUX_LOAD);
+    template <int AUX = MDSP_IO_AUX_LOAD> static __device__ __forceinline__ double load(__amdgpu_buffer_rsrc_t r, int off) {
+        const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, AUX);
         return __hiloint2double((int)v.y, (int)v.x);
     }
-    static __device__ __forceinline__ void store(double d, __amdgpu_buffer_rsrc_t r, int off) {
+    template <int AUX = MDSP_IO_AUX_STORE> static __device__ __forceinline__ void store(double d, __amdgpu_buffer_rsrc_t r, int off) {
         u2 v;
         v.x = (unsigned)__double2loint(d);
         v.y = (unsigned)__double2hiint(d);
-        __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, MDSP_IO_AUX_STORE);
+        __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, AUX);
     }
 };
 template <> struct Ld<cx<float>> {
     typedef unsigned u2 __attribute__((ext_vector_type(2)));
-    static __device__ __forceinline__ cx<float> load(__amdgpu_buffer_rsrc_t r, int off) {
-        const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, MDSP_IO_AUX_LOAD);
+    template <int AUX = MDSP_IO_AUX_LOAD> static __device__ __forceinline__ cx<float> load(__amdgpu_buffer_rsrc_t r, int off) {
+        const u2 v = __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, AUX);
         return {__uint_as_float(v.x), __uint_as_float(v.y)};
     }
-    static __device__ __forceinline__ void store(cx<float> c, __amdgpu_buffer_rsrc_t r, int off) {
+    template <int AUX = MDSP_IO_AUX_STORE> static __device__ __forceinline__ void store(cx<float> c, __amdgpu_buffer_rsrc_t r, int off) {
         u2 v;
         v.x = __float_as_uint(c.x);
         v.y = __float_as_uint(c.y);
-        __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, MDSP_IO_AUX_STORE);
+        __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, AUX);
     }
 };
 template <> struct Ld<cx<double>> {
     typedef unsigned u4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ cx<double> load(__amdgpu_buffer_rsrc_t r, int off) {
-        const u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, MDSP_IO_AUX_LOAD);
+    template <int AUX = MDSP_IO_AUX_LOAD> static __device__ __forceinline__ cx<double> load(__amdgpu_buffer_rsrc_t r, int off) {
+        const u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, AUX);
         return {__hiloint2double((int)v.y, (int)v.x), __hiloint2double((int)v.w, (int)v.z)};
     }
-    static __device__ __forceinline__ void store(cx<double> c, __amdgpu_buffer_rsrc_t r, int off) {
+    template <int AUX = MDSP_IO_AUX_STORE> static __device__ __forceinline__ void store(cx<double> c, __amdgpu_buffer_rsrc_t r, int off) {
         u4 v;
         v.x = (unsigned)__double2loint(c.x);
         v.y = (unsigned)__double2hiint(c.x);
         v.z = (unsigned)__double2loint(c.y);
         v.w = (unsigned)__double2hiint(c.y);
-        __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, MDSP_IO_AUX_STORE);
+        __builtin_amdgcn_raw_buffer_store_b128(v, r, off, 0, AUX);
     }
 };
 
@@ -95,82 +96,82 @@ template <> struct Ld<cx<double>> {
 //     skipped by wave-uniform branches and the one straddling group uses the OOB sentinel per lane.
 //   * past-the-end elements are handled by the descriptor's num_records (reads 0 / store dropped).
 // All per-element offsets are one VGPR (t*SZ) plus immediates; nothing per-element is loop-invariant state.
-template <typename T, int E, int TT> __device__ __forceinline__ void load_window(T (&out)[E], __amdgpu_buffer_rsrc_t r, int lead, int t) {
+template <typename T, int E, int TT, int AUX = MDSP_IO_AUX_LOAD> __device__ __forceinline__ void load_window(T (&out)[E], __amdgpu_buffer_rsrc_t r, int lead, int t) {
     constexpr int SZ = (int)sizeof(T);
     int off = t * SZ;
     asm volatile("" : "+v"(off));  // keep LICM from materialising E offset VGPRs outside the persistent loop
     if (lead == 0) {               // wave-uniform; the steady state: one VGPR offset + immediates, no per-lane tests
 #pragma unroll
-        for (int e = 0; e < E; ++e) out[e] = Ld<T>::load(r, off + TT * e * SZ);
+        for (int e = 0; e < E; ++e) out[e] = Ld<T>::template load<AUX>(r, off + TT * e * SZ);
     } else {                       // leading blocks only: lanes in front of the signal read through the OOB sentinel (-> 0)
 #pragma unroll
-        for (int e = 0; e < E; ++e) out[e] = Ld<T>::load(r, (t + TT * e) < lead ? OOB : off + TT * e * SZ);
+        for (int e = 0; e < E; ++e) out[e] = Ld<T>::template load<AUX>(r, (t + TT * e) < lead ? OOB : off + TT * e * SZ);
     }
 }
 
 // elements e = E0 .. E-1 only (the tail of a window whose head is already in registers)
-template <typename T, int E, int TT, int E0> __device__ __forceinline__ void load_window_tail(T (&out)[E], __amdgpu_buffer_rsrc_t r, int t) {
+template <typename T, int E, int TT, int E0, int AUX = MDSP_IO_AUX_LOAD> __device__ __forceinline__ void load_window_tail(T (&out)[E], __amdgpu_buffer_rsrc_t r, int t) {
     constexpr int SZ = (int)sizeof(T);
     int off = t * SZ;
     asm volatile("" : "+v"(off));
 #pragma unroll
-    for (int e = E0; e < E; ++e) out[e] = Ld<T>::load(r, off + TT * e * SZ);
+    for (int e = E0; e < E; ++e) out[e] = Ld<T>::template load<AUX>(r, off + TT * e * SZ);
 }
 
 // elements e = 0 .. E0-1 only (the head of a window that could not be taken from the previous one)
-template <typename T, int E, int TT, int E0> __device__ __forceinline__ void load_window_head(T (&out)[E], __amdgpu_buffer_rsrc_t r, int t) {
+template <typename T, int E, int TT, int E0, int AUX = MDSP_IO_AUX_LOAD> __device__ __forceinline__ void load_window_head(T (&out)[E], __amdgpu_buffer_rsrc_t r, int t) {
     constexpr int SZ = (int)sizeof(T);
     int off = t * SZ;
     asm volatile("" : "+v"(off));
 #pragma unroll
-    for (int e = 0; e < E0; ++e) out[e] = Ld<T>::load(r, off + TT * e * SZ);
+    for (int e = 0; e < E0; ++e) out[e] = Ld<T>::template load<AUX>(r, off + TT * e * SZ);
 }
 
 // Stores of elements E0 .. E-1 of a window whose dropped lead is exactly E0 whole elements (E0 TT samples): plain stores, no per-lane test
-template <typename T, int E, int TT, int E0, typename F> __device__ __forceinline__ void store_window_tail(F&& get, __amdgpu_buffer_rsrc_t w, int t) {
+template <typename T, int E, int TT, int E0, int AUX = MDSP_IO_AUX_STORE, typename F> __device__ __forceinline__ void store_window_tail(F&& get, __amdgpu_buffer_rsrc_t w, int t) {
     constexpr int SZ = (int)sizeof(T);
     int off = t * SZ;
     asm volatile("" : "+v"(off));
 #pragma unroll
-    for (int e = E0; e < E; ++e) Ld<T>::store(get(e), w, off + TT * e * SZ);
+    for (int e = E0; e < E; ++e) Ld<T>::template store<AUX>(get(e), w, off + TT * e * SZ);
 }
 
 // Stores of elements ES .. E-1 of a window whose first `lead` elements are dropped, with ES = lead div TT known at compile time: elements above
 // ES are plain stores (one VGPR offset + immediates), element ES drops its lanes t < lead - ES TT through the OOB sentinel, elements below ES
 // issue nothing at all.
-template <typename T, int E, int TT, int ES, typename F> __device__ __forceinline__ void store_window_from(F&& get, __amdgpu_buffer_rsrc_t w, int rem, int t, int off) {
+template <typename T, int E, int TT, int ES, int AUX = MDSP_IO_AUX_STORE, typename F> __device__ __forceinline__ void store_window_from(F&& get, __amdgpu_buffer_rsrc_t w, int rem, int t, int off) {
     constexpr int SZ = (int)sizeof(T);
-    Ld<T>::store(get(ES), w, t < rem ? OOB : off + TT * ES * SZ);
+    Ld<T>::template store<AUX>(get(ES), w, t < rem ? OOB : off + TT * ES * SZ);
 #pragma unroll
-    for (int e = ES + 1; e < E; ++e) Ld<T>::store(get(e), w, off + TT * e * SZ);
+    for (int e = ES + 1; e < E; ++e) Ld<T>::template store<AUX>(get(e), w, off + TT * e * SZ);
 }
-template <typename T, int E, int TT, int ES, typename F> __device__ __forceinline__ void store_window_switch(F&& get, __amdgpu_buffer_rsrc_t w, int es, int rem, int t, int off) {
+template <typename T, int E, int TT, int ES, int AUX = MDSP_IO_AUX_STORE, typename F> __device__ __forceinline__ void store_window_switch(F&& get, __amdgpu_buffer_rsrc_t w, int es, int rem, int t, int off) {
     if constexpr (ES < E) {
-        if (es == ES) store_window_from<T, E, TT, ES>(get, w, rem, t, off);
-        else store_window_switch<T, E, TT, ES + 1>(get, w, es, rem, t, off);
+        if (es == ES) store_window_from<T, E, TT, ES, AUX>(get, w, rem, t, off);
+        else store_window_switch<T, E, TT, ES + 1, AUX>(get, w, es, rem, t, off);
     }
 }
 
 #ifndef MDSP_IO_STORE_SWITCH
 #define MDSP_IO_STORE_SWITCH 1   // 0: the round-2 form (one compare + select per element and store)
 #endif
-template <typename T, int E, int TT, typename F> __device__ __forceinline__ void store_window(F&& get, __amdgpu_buffer_rsrc_t w, int lead, int t) {
+template <typename T, int E, int TT, int AUX = MDSP_IO_AUX_STORE, typename F> __device__ __forceinline__ void store_window(F&& get, __amdgpu_buffer_rsrc_t w, int lead, int t) {
     constexpr int SZ = (int)sizeof(T);
     int off = t * SZ;
     asm volatile("" : "+v"(off));
     if (lead == 0) {
 #pragma unroll
-        for (int e = 0; e < E; ++e) Ld<T>::store(get(e), w, off + TT * e * SZ);
+        for (int e = 0; e < E; ++e) Ld<T>::template store<AUX>(get(e), w, off + TT * e * SZ);
     } else if (MDSP_IO_STORE_SWITCH && (TT & (TT - 1)) == 0) {
         // `lead` is wave-uniform (and loop-invariant in the overlap-save kernels: nb - 1): which elements lie wholly below it is a scalar
         // decision, so the per-element compare + select of the branch-free form (2 VALU operations per store, 8 % of the overlap-save
         // kernel's vector instructions) shrinks to ONE select for the element that straddles `lead`, and the dropped elements cost no
         // VMEM slot either.  The chain of wave-uniform compares runs on the scalar unit.
         const int es = __builtin_amdgcn_readfirstlane(lead / TT), rem = __builtin_amdgcn_readfirstlane(lead - (lead / TT) * TT);
-        store_window_switch<T, E, TT, 0>(get, w, es, rem, t, off);   // es >= E: the whole window is dropped
+        store_window_switch<T, E, TT, 0, AUX>(get, w, es, rem, t, off);   // es >= E: the whole window is dropped
     } else {                       // branch-free: lanes below `lead` store through the OOB sentinel (dropped)
 #pragma unroll
-        for (int e = 0; e < E; ++e) Ld<T>::store(get(e), w, (t + TT * e) < lead ? OOB : off + TT * e * SZ);
+        for (int e = 0; e < E; ++e) Ld<T>::template store<AUX>(get(e), w, (t + TT * e) < lead ? OOB : off + TT * e * SZ);
     }
 }
 

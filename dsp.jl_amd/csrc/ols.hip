@@ -175,7 +175,9 @@ __device__ __forceinline__ void ols_issue_loads(OlsRaw<R, E, CPLX>& raw, const O
 // b[t + T e], e < K, IS a[t + T (E - K + e)] -- and the first K elements of the NEXT consecutive unit's block a are this unit's b[E - K .. E), still
 // in raw.b when that unit is loaded (`cont`, wave-uniform: same column, next pair, this unit had its second block).  Every sample is requested
 // once, and every window starts K T samples in front of a multiple of (E - K) T: on a 128-byte line when the column does.
-template <typename R, int E, int T, int K>
+// AUXL: cache policy of the loads that are a sample's only request (devio.h); the lead elements of a run or column start, which the slot in front reads
+// too, stay plain.
+template <typename R, int E, int T, int K, int AUXL = MDSP_IO_AUX_LOAD>
 __device__ __forceinline__ void ols_issue_loads_tiled(OlsRaw<R, E, false>& raw, const OlsFusedArgs& a, OlsPos q, bool cont, int t) {
     constexpr int64_t SZ = (int64_t)sizeof(R);
     const R* xc = static_cast<const R*>(a.x) + q.col * a.ldx;
@@ -192,15 +194,15 @@ __device__ __forceinline__ void ols_issue_loads_tiled(OlsRaw<R, E, false>& raw, 
     } else {
         io::load_window_head<R, E, T, K>(raw.a, ra, t);
     }
-    io::load_window_tail<R, E, T, K>(raw.a, ra, t);
+    io::load_window_tail<R, E, T, K, AUXL>(raw.a, ra, t);
     const int64_t startB = start + a.L;
     const __amdgpu_buffer_rsrc_t rb = io::make_rsrc(xc + startB, haveB ? (a.nx - startB) * SZ : 0);
-    io::load_window_tail<R, E, T, K>(raw.b, rb, t);
+    io::load_window_tail<R, E, T, K, AUXL>(raw.b, rb, t);
 #pragma unroll
     for (int e = 0; e < K; ++e) raw.b[e] = haveB ? raw.a[E - K + e] : (R)0;   // no second block: zeros, as its descriptor of no bytes returns them
 }
 
-template <typename R, int E, int T, bool CPLX, int KT = -1>
+template <typename R, int E, int T, bool CPLX, int KT = -1, int AUXS = MDSP_IO_AUX_STORE>   // AUXS: the KT >= 0 (tiled) stores only
 __device__ __forceinline__ void ols_store(const cx<R> (&v)[E], const OlsFusedArgs& a, OlsPos q, int t) {
     using TT = std::conditional_t<CPLX, cx<R>, R>;
     constexpr int64_t SZ = (int64_t)sizeof(TT);
@@ -209,10 +211,10 @@ __device__ __forceinline__ void ols_store(const cx<R> (&v)[E], const OlsFusedArg
     TT* yc = static_cast<TT*>(a.y) + q.col * a.ldy;
     if constexpr (KT >= 0) {                            // elements KT .. E-1 of both windows: plain stores, nothing straddles
         const __amdgpu_buffer_rsrc_t w = io::make_rsrc(yc + off0 - lead, q.live ? (a.nout - off0 + lead) * SZ : 0);
-        io::store_window_tail<TT, E, T, KT>([&](int e) { return v[e].x; }, w, t);
+        io::store_window_tail<TT, E, T, KT, AUXS>([&](int e) { return v[e].x; }, w, t);
         const int64_t offB = off0 + a.L;
         const __amdgpu_buffer_rsrc_t wb = io::make_rsrc(yc + offB - lead, (q.live && offB < a.nout) ? (a.nout - offB + lead) * SZ : 0);
-        io::store_window_tail<TT, E, T, KT>([&](int e) { return v[e].y; }, wb, t);
+        io::store_window_tail<TT, E, T, KT, AUXS>([&](int e) { return v[e].y; }, wb, t);
         return;
     }
     {
@@ -229,11 +231,14 @@ __device__ __forceinline__ void ols_store(const cx<R> (&v)[E], const OlsFusedArg
 
 // FOLD: the folded butterflies (fft_lds.h: products that only feed an add / subtract pair ride in it), the spectrum product inside the inverse's pass 0
 // TILED: windows of E - K whole elements with a lead of K = 2 (ols_issue_loads_tiled); a.lead == K T, a.L == (E - K) T
-template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false, bool TILED = false>
+// AUXL, AUXS: cache policy of the TILED form's 28 + 28 streaming loads and stores per unit (every other access, and every other form, is plain)
+template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false, bool TILED = false,
+          int AUXL = MDSP_IO_AUX_LOAD, int AUXS = MDSP_IO_AUX_STORE>
 __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs a) {
     static_assert(!ROWS || (CPLX && !HREG), "the rows form: complex blocks, one spectrum row per block");
     static_assert(!FOLD || (HREG && NBUF == 1 && E == 16), "the folded form: spectrum in registers, one LDS buffer");
     static_assert(!TILED || (FOLD && !CPLX && !PREFETCH && E == 16), "the tiled form: the folded kernel of real blocks, loads at the top of the iteration");
+    static_assert(TILED || (AUXL == MDSP_IO_AUX_LOAD && AUXS == MDSP_IO_AUX_STORE), "a cache policy of its own: the tiled form only");
     constexpr int K = 2;   // TILED: elements of lead
     using C = fft::Cfg<N, E>;
     constexpr int T = C::T, PADSHIFT = 4;
@@ -270,7 +275,7 @@ __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs 
                 if (a.memprio & 1) __builtin_amdgcn_s_setprio(3);
                 if constexpr (TILED) {
                     const bool cont = cur.live && cur.col == held_col && cur.p == held_p + 1;
-                    ols_issue_loads_tiled<R, E, T, K>(raw, a, cur, cont, t);
+                    ols_issue_loads_tiled<R, E, T, K, AUXL>(raw, a, cur, cont, t);
                     const bool haveB = cur.live && (2 * cur.p + 1) < a.nblocks;
                     held_col = haveB ? cur.col : -1;
                     held_p = cur.p;
@@ -325,7 +330,7 @@ __global__ __launch_bounds__((N / E) * G, 2) void ols_fused_kernel(OlsFusedArgs 
         // exchanges of a unit alternate buffers so the next unit's first write is two barriers behind its readers
         if (!MDSP_ABLATED(a, 4)) {
             if (a.memprio & 2) __builtin_amdgcn_s_setprio(3);
-            ols_store<R, E, T, CPLX, TILED ? K : -1>(v, a, cur, t);
+            ols_store<R, E, T, CPLX, TILED ? K : -1, AUXS>(v, a, cur, t);
             if (a.memprio & 2) __builtin_amdgcn_s_setprio(0);
         }
         cur = nxt;
@@ -798,9 +803,10 @@ template <typename R> int upload_table(DevBuf& buf, int64_t n) {
 }
 
 // ---- fused launch ---------------------------------------------------------------------------------------
-template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false, bool TILED = false>
+template <typename R, int N, int E, int G, int TWMODE, bool CPLX, int NBUF, bool PREFETCH, bool HREG = true, bool ROWS = false, bool FOLD = false, bool TILED = false,
+          int AUXL = MDSP_IO_AUX_LOAD, int AUXS = MDSP_IO_AUX_STORE>
 int launch_fused_geo(const OlsFusedArgs& a, hipStream_t s) {
-    auto kern = ols_fused_kernel<R, N, E, G, TWMODE, CPLX, NBUF, PREFETCH, HREG, ROWS, FOLD, TILED>;
+    auto kern = ols_fused_kernel<R, N, E, G, TWMODE, CPLX, NBUF, PREFETCH, HREG, ROWS, FOLD, TILED, AUXL, AUXS>;
     constexpr int threads = (N / E) * G;
     int per_cu = 0;
     MDSP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0));
@@ -844,7 +850,28 @@ int ols_rows_impl(int dbl, void* work, int64_t rows, int hrows, const void* Hrow
     return launch_fused_geo<float, 8192, 16, 1, 1, true, 1, false, false, true>(a, st);
 }
 
-template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a, hipStream_t s, bool tiled) {
+// The streaming form of the tiled headline kernel (profiles/ols_stream_ab.json): nontemporal loads and nontemporal stores, the policy of the
+// fastest float4 copy on the same buffers.  The release library carries the plain form and this one; -DMDSP_DEBUG_KNOBS builds carry the whole matrix,
+// loads {0, 2 nt, 3 sc0|nt} x stores {0, 2 nt, 17 sc0|sc1, 18 nt|sc1}, selected by MDSP_OLS_AUX = 100 loads + stores (e.g. 217; -1, the default: what the rule says).
+constexpr int kOlsStreamAuxL = 2, kOlsStreamAuxS = 2;
+template <typename R, int N, int AUXL, int AUXS> int launch_fused_tiled(const OlsFusedArgs& a, hipStream_t s) {
+    return launch_fused_geo<R, N, 16, 1, 1, false, 1, false, true, false, true, true, AUXL, AUXS>(a, s);
+}
+#ifdef MDSP_DEBUG_KNOBS
+template <typename R, int N, int AUXL> int launch_fused_tiled_stores(int auxs, const OlsFusedArgs& a, hipStream_t s) {
+    switch (auxs) {
+        case 0: return launch_fused_tiled<R, N, AUXL, 0>(a, s);
+        case 2: return launch_fused_tiled<R, N, AUXL, 2>(a, s);
+        case 17: return launch_fused_tiled<R, N, AUXL, 17>(a, s);
+        case 18: return launch_fused_tiled<R, N, AUXL, 18>(a, s);
+        default: break;
+    }
+    MDSP_FAIL(MDSP_ERR_ARGUMENT, "MDSP_OLS_AUX: stores must be one of 0, 2, 17, 18; got %d", auxs);
+}
+#endif
+
+// stream: the footprint rule's answer for this launch (ols_plan.h); only a tiled launch has a streaming instantiation
+template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a, hipStream_t s, bool tiled, bool stream) {
     // Geometry: E elements per thread so that a transform owns whole wavefronts (T = N/E >= 64); G transforms
     // per workgroup so that workgroups have 256 threads where possible.
     constexpr bool DBL = sizeof(R) == 8;
@@ -870,7 +897,19 @@ template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a
     if constexpr (N == 2048 && !CPLX && !DBL) {
         if (tiled) {
             if (a.lead != 2 * 128 || a.L != 14 * 128) MDSP_FAIL(MDSP_ERR_ASSERTION, "tiled overlap-save launch with tile %lld, lead %d", (long long)a.L, a.lead);
-            return launch_fused_geo<R, N, 16, 1, 1, CPLX, 1, false, true, false, true, true>(a, s);
+#ifdef MDSP_DEBUG_KNOBS
+            if (const int aux = MDSP_DBG(ols_aux); aux >= 0) {
+                switch (aux / 100) {
+                    case 0: return launch_fused_tiled_stores<R, N, 0>(aux % 100, a, s);
+                    case 2: return launch_fused_tiled_stores<R, N, 2>(aux % 100, a, s);
+                    case 3: return launch_fused_tiled_stores<R, N, 3>(aux % 100, a, s);
+                    default: break;
+                }
+                MDSP_FAIL(MDSP_ERR_ARGUMENT, "MDSP_OLS_AUX: loads must be one of 0, 2, 3; got %d", aux / 100);
+            }
+#endif
+            if (stream) return launch_fused_tiled<R, N, kOlsStreamAuxL, kOlsStreamAuxS>(a, s);
+            return launch_fused_tiled<R, N, MDSP_IO_AUX_LOAD, MDSP_IO_AUX_STORE>(a, s);
         }
         return launch_fused_geo<R, N, 16, 1, 1, CPLX, 1, false, true, false, true>(a, s);
     } else {
@@ -884,15 +923,15 @@ template <typename R, int N, bool CPLX> int launch_fused_n(const OlsFusedArgs& a
     }
 }
 
-template <typename R, bool CPLX> int launch_fused(int64_t nfft, const OlsFusedArgs& a, hipStream_t s, bool tiled = false) {
+template <typename R, bool CPLX> int launch_fused(int64_t nfft, const OlsFusedArgs& a, hipStream_t s, bool tiled = false, bool stream = false) {
     switch (nfft) {
-        case 256: return launch_fused_n<R, 256, CPLX>(a, s, tiled);
-        case 512: return launch_fused_n<R, 512, CPLX>(a, s, tiled);
-        case 1024: return launch_fused_n<R, 1024, CPLX>(a, s, tiled);
-        case 2048: return launch_fused_n<R, 2048, CPLX>(a, s, tiled);
-        case 4096: return launch_fused_n<R, 4096, CPLX>(a, s, tiled);
+        case 256: return launch_fused_n<R, 256, CPLX>(a, s, tiled, stream);
+        case 512: return launch_fused_n<R, 512, CPLX>(a, s, tiled, stream);
+        case 1024: return launch_fused_n<R, 1024, CPLX>(a, s, tiled, stream);
+        case 2048: return launch_fused_n<R, 2048, CPLX>(a, s, tiled, stream);
+        case 4096: return launch_fused_n<R, 4096, CPLX>(a, s, tiled, stream);
         case 8192:
-            if constexpr (sizeof(R) == 4) return launch_fused_n<R, 8192, CPLX>(a, s, tiled);
+            if constexpr (sizeof(R) == 4) return launch_fused_n<R, 8192, CPLX>(a, s, tiled, stream);
         default: break;
     }
     MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "fused overlap-save does not support nfft=%lld", (long long)nfft);
@@ -1129,6 +1168,16 @@ int mdsp_ols_tile_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int 
     return MDSP_OK;
 }
 
+// The footprint rule (ols_plan.h) for a whole-column launch of a tiled plan.  Only real Float32 plans can be tiled (ols_tile_rule), and none is with
+// MDSP_OLS_TILE = 0.
+int mdsp_ols_stream_for(int64_t nx, int64_t nout, int64_t columns, int dtype, int* streaming) {
+    if (!dtype_valid(dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid dtype %d", dtype);
+    if (nx < 0 || nout < 0 || columns < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "negative size");
+    const bool can_tile = dtype == MDSP_F32 && tunables().ols_tile == 1;
+    if (streaming) *streaming = mdsp::ols_stream_rule(tunables().ols_stream, can_tile, nx, nout, columns, (int64_t)dtype_size(dtype)) ? 1 : 0;
+    return MDSP_OK;
+}
+
 int mdsp_ols_geometry_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int mode, int engine, int64_t* exec_nfft, int64_t* exec_block_len, int* partitions,
                           int* engine_used, int* rows) {
     OlsChoice c;
@@ -1330,7 +1379,12 @@ static int ols_exec_core(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int6
     a.ablate = MDSP_DBG(ablate);
     a.memprio = tunables().ols_prio;
     if (cplx) return dbl ? launch_fused<double, true>(plan->nfft, a, s) : launch_fused<float, true>(plan->nfft, a, s);
-    return dbl ? launch_fused<double, false>(plan->nfft, a, s) : launch_fused<float, false>(plan->nfft, a, s, tile_grid && plan->tiled);
+    const bool tiled = tile_grid && plan->tiled;
+    // what this launch touches (block ranges: the range's own samples, not the column's): tiles [g_begin, g_end) read from tile_lead in front of the first
+    const int64_t nread = std::max<int64_t>(0, std::min(nx, g_end * Lg) - std::max<int64_t>(0, g_begin * Lg - a.lead));
+    const int64_t nwritten = std::max<int64_t>(0, std::min(nout, g_end * Lg) - g_begin * Lg);
+    const bool stream = mdsp::ols_stream_rule(tunables().ols_stream, tiled, nread, nwritten, ncols, (int64_t)dtype_size(plan->dtype));
+    return dbl ? launch_fused<double, false>(plan->nfft, a, s) : launch_fused<float, false>(plan->nfft, a, s, tiled, stream);
 }
 
 int mdsp_ols_exec(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx, void* y_dev, int64_t nout, int64_t ldy,

@@ -30,6 +30,17 @@ struct mdsp_ols_plan_s {
 };
 
 namespace mdsp {
+// The footprint rule of the tiled kernel's streaming cache policy (AUXL / AUXS of ols_fused_kernel).  A streaming policy is right only when
+// nothing the launch touches can still be in cache for its consumer: the streaming instantiation runs when the bytes the launch reads plus the bytes it
+// writes exceed 512 MiB, twice the Infinity Cache (measured: at exactly 512 MiB streaming lost one round of sixteen), the plain one up to that -- small signals, the chunks of mdsp_ols_exec_host.  `knob` is MDSP_OLS_STREAM, read
+// at launch: 1 this rule, 0 always plain, 2 always streaming (tests, A/B).  Only tiled launches have a streaming instantiation.
+constexpr int64_t kOlsStreamBytes = int64_t(512) << 20;
+inline bool ols_stream_rule(int knob, bool tiled, int64_t nread, int64_t nwritten, int64_t columns, int64_t elem_bytes) {
+    if (!tiled || knob == 0) return false;
+    if (knob == 2) return true;
+    return (nread + nwritten) * columns * elem_bytes > kOlsStreamBytes;
+}
+
 // Tiles [first_tile, first_tile + ntiles) of the grid the whole-column call runs for one column of nx samples / nout outputs, from a slice of the signal:
 // xs_dev holds x[xs_first .. xs_first + xs_len) and covers [first_tile tile - tile_lead, (first_tile + ntiles) tile) clipped to [0, nx); ys_dev[0..] receives
 // the outputs from first_tile tile on.  first_tile even for real dtypes on single-block plans.  Bit-identical to the whole-column call (mdsp_ols_exec_host).

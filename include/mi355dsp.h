@@ -136,6 +136,11 @@ int mdsp_ols_geometry_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, 
  * MDSP_OLS_TILE = 0 (mdsp_set_knob, before the plan is made) switches the rule off.  mdsp_ols_tile_for: the same answer without a plan or a device. */
 int mdsp_ols_plan_tile(mdsp_ols_plan plan, int64_t* tile_len, int64_t* tile_lead);
 int mdsp_ols_tile_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int mode, int engine, int64_t* tile_len, int64_t* tile_lead);
+/* The cache policy of a tiled plan's launches: *streaming = 1 when a whole-column call over `columns` columns of nx samples / nout outputs
+ * runs the kernel whose loads and stores bypass the caches (same arithmetic, bit-identical outputs).  Knob MDSP_OLS_STREAM (mdsp_set_knob, read at launch):
+ * 1 = the footprint rule (the default) -- launches that read and write more than 512 MiB, (nx + nout) columns 4 bytes, which nothing can still hold in
+ * cache for a consumer --, 0 = never, 2 = every launch of a tiled plan.  Always 0 for dtypes that have no tiled plans and under MDSP_OLS_TILE = 0.  No device. */
+int mdsp_ols_stream_for(int64_t nx, int64_t nout, int64_t columns, int dtype, int* streaming);
 /* x_dev: (nx, ncols) ld ldx;  y_dev: (nout, ncols) ld ldy.  nout = nx (filt), nx+nb-1 (conv), or any
  * 0 <= nout <= nx+nb-1.  x and y must not alias (Filters/filt.jl:438-439). */
 int mdsp_ols_exec(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx, void* y_dev,

@@ -253,6 +253,12 @@ function ols_tile_for(nb::Integer, nfft::Integer, nx::Integer, ::Type{T}, mode::
                 nb, nfft, nx, mdtype(T), mode, engine, tile, lead))
     (tile = Int(tile[]), lead = Int(lead[]))
 end
+# whether a launch of a tiled plan over `columns` columns of nx samples / nout outputs runs the streaming cache policy (the footprint rule, knob MDSP_OLS_STREAM)
+function ols_stream_for(nx::Integer, nout::Integer, columns::Integer, ::Type{T}) where {T}
+    streaming = Ref{Cint}(0)
+    check(ccall((:mdsp_ols_stream_for, lib), Cint, (Int64, Int64, Int64, Cint, Ref{Cint}), nx, nout, columns, mdtype(T), streaming))
+    streaming[] != 0
+end
 
 # The function-style entry points build a plan per call in the reference (cheap FFTW plans); here the plan comes from the LIBRARY's LRU
 # (mdsp_ols_plan_cached: keyed by device, thread, stream and the contents of the taps) -- ~45 us per call instead of ~1 ms.  The handle is
