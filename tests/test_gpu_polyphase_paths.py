@@ -42,6 +42,13 @@ def torch():
     return t
 
 
+def stream_length(tp, L, M, nch, cplx, budget=BUDGET):
+    """Samples per channel: several tiles where the reference's cost (budget long-double multiply-adds) allows, and always past the history and a few
+    decimation steps.  mdsp_fir_kernel_path depends on it: tests/test_gpu_guard_misc.py takes its lengths from here too."""
+    per_out = tp * nch * (2 if cplx else 1)
+    return int(min(200_000, max(budget / per_out * M / L, tp + 4 * M + 300)))
+
+
 def _case_id(c):
     L, M, hlen, td, xd, knobs, taps, path = c
     kn = "-".join(f"{k.replace('MDSP_FIR_', '').lower()}{v}" for k, v in knobs)
@@ -75,9 +82,7 @@ def test_polyphase_path_against_extended_precision_reference(d, torch, case):
     tdev = {np.float32: torch.float32, np.float64: torch.float64, np.complex64: torch.complex64, np.complex128: torch.complex128}
     rdt = np.float64 if dbl else np.float32
     tp = -(-hlen // L)
-    # stream length: several tiles where the reference's cost allows, and always past the history and a few decimation steps
-    per_out = tp * NCH * (2 if cplx else 1)
-    n = int(min(200_000, max(BUDGET / per_out * M / L, tp + 4 * M + 300)))
+    n = stream_length(tp, L, M, NCH, cplx)
     x = rng.standard_normal((NCH, n))
     if cplx:
         x = x + 1j * rng.standard_normal((NCH, n))
