@@ -18,6 +18,7 @@ OK, ERR_ARGUMENT, ERR_DOMAIN, ERR_DIMENSION, ERR_ASSERTION, ERR_UNSUPPORTED, ERR
 F32, F64, C32, C64 = 0, 1, 2, 3
 ENGINE_AUTO, ENGINE_FUSED, ENGINE_ROCFFT = 0, 1, 2
 OLS_FILT, OLS_CONV = 0, 1
+UNWRAP_CONTIGUOUS, UNWRAP_STRIDED = 0, 1
 HOST_PINNED = 1
 COMM_ID_BYTES = 128
 
@@ -117,6 +118,12 @@ PROTOTYPES = {
     "mdsp_periodogram2_plan_info": (ci, [vp, pi64, pi64, pint]),
     "mdsp_periodogram2_exec": (ci, [vp, vp, i64, vp, i64, vp]),
     "mdsp_periodogram2_geometry_for": (ci, [i64, i64, pi64, pi64, pi64]),
+    "mdsp_unwrap_plan_create": (ci, [pvp, i64, i64, i64, ci, cd, i64]),
+    "mdsp_unwrap_plan_destroy": (ci, [vp]),
+    "mdsp_unwrap_plan_info": (ci, [vp, pint, pi64, pi64, pi64]),
+    "mdsp_unwrap_exec": (ci, [vp, vp, vp, vp]),
+    "mdsp_unwrap_geometry_for": (ci, [i64, i64, i64, ci, i64, pint, pi64, pi64, pi64]),
+    "mdsp_unwrap_emulate_host": (ci, [vp, vp, i64, i64, i64, ci, cd, i64]),
     "mdsp_tdfir_state_exec": (ci, [vp, i64, ci, vp, i64, i64, i64, vp, i64, vp, vp]),
     "mdsp_tdfir_state_exec_t": (ci, [vp, i64, ci, ci, vp, i64, i64, i64, vp, i64, vp, vp]),
     "mdsp_extrapolate": (ci, [vp, i64, i64, i64, ci, i64, vp, i64, vp]),

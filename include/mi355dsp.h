@@ -317,6 +317,41 @@ int mdsp_periodogram2_exec(mdsp_periodogram2_plan plan, const void* s_dev, int64
 int mdsp_periodogram2_geometry_for(int64_t nfft1, int64_t nfft2, int64_t* kmax, int64_t* wc_host, int64_t* partials);
 
 /* ------------------------------------------------------------------------------------------------------
+ * unwrap / unwrap! along one dimension (src/unwrap.jl:17-34, `dims::Integer`): accumulate!(unwrap_kernel(range), y, m; dims)
+ *   y[0] = m[0],  y[i] = m[i] - round((m[i] - y[i-1]) / range) * range   along j of an (inner, len, outer) array, element (i, j, o) at
+ *   i + inner (j + len o): a Julia array unwrapped along dimension d has inner = prod(size[1:d-1]), len = size[d], outer = prod(size[d+1:end]);
+ *   a C-ordered array the same with the axes read from the last to the first.  No transposes: inner == 1 is the contiguous route
+ *   (MDSP_UNWRAP_CONTIGUOUS), inner > 1 the strided one (MDSP_UNWRAP_STRIDED, coalesced across inner).
+ *   Evaluated as an integer prefix sum K of d_i = rint((m[i] - m[i-1]) / range), y[i] = m[i] - T(K_i) range, every operation rounded in T as
+ *   the reference's: bit-identical to the serial recurrence whenever no (m[i] - m[i-1]) / range lies near a rounding tie; near a tie the two
+ *   forms may differ by whole periods from that sample on.  Documented range |K| < 2^24 (Float32) / 2^53 (Float64);
+ *   beyond it the result is unspecified (the reference's own K no longer holds integers), the call stays inside its arrays.  A non-finite
+ *   m[i], i >= 1, makes the rest of its line NaN, m[0] = NaN the whole line, m[0] = +-Inf followed by finite samples a line of +-Inf.
+ *   dtype MDSP_F32 / MDSP_F64; range is converted to that type and must be finite and nonzero there.  segments: 0 = the library cuts a line
+ *   into S segments when the lines alone do not fill the device; > 0 forces the cut (clamped to len; 1 when len <= 2; segments are
+ *   ceil(len / segments) long, the last one ragged, and S counts the non-empty ones).  S == 1 is one launch; S > 1 three launches on the
+ *   caller's stream (segment sums, carries, apply) and 24 bytes of workspace per segment and line.  No atomics and no waiting between
+ *   workgroups: one plan gives bit-identical results exec after exec, and every cut gives the same bits.
+ *   Checks, before any launch: sizes < 0, a dtype that is not real floating, range non-finite or 0: MDSP_ERR_ARGUMENT; any size == 0 succeeds
+ *   without a launch; len == 1 is a copy.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { MDSP_UNWRAP_CONTIGUOUS = 0, MDSP_UNWRAP_STRIDED = 1 };
+typedef struct mdsp_unwrap_plan_s* mdsp_unwrap_plan;
+int mdsp_unwrap_plan_create(mdsp_unwrap_plan* plan, int64_t inner, int64_t len, int64_t outer, int dtype, double range, int64_t segments);
+int mdsp_unwrap_plan_destroy(mdsp_unwrap_plan plan);
+int mdsp_unwrap_plan_info(mdsp_unwrap_plan plan, int* route, int64_t* nsegments, int64_t* seglen, int64_t* workspace_bytes);
+/* out_dev == in_dev is unwrap!(m); any other overlap of the two arrays is MDSP_ERR_ARGUMENT. */
+int mdsp_unwrap_exec(mdsp_unwrap_plan plan, const void* in_dev, void* out_dev, void* stream);
+/* Pure host arithmetic, no device needed: the route, S, the segment length and the workspace a plan for these arguments has.  Any output
+ * pointer may be NULL. */
+int mdsp_unwrap_geometry_for(int64_t inner, int64_t len, int64_t outer, int dtype, int64_t segments, int* route, int64_t* nsegments,
+                             int64_t* seglen, int64_t* workspace_bytes);
+/* Host emulation of the device code (no device): the same geometry and the same operator and per-segment walk (csrc/unwrap_scan.h) on host
+ * arrays, the three steps one after the other.  out_host may be in_host. */
+int mdsp_unwrap_emulate_host(const void* in_host, void* out_host, int64_t inner, int64_t len, int64_t outer, int dtype, double range,
+                             int64_t segments);
+
+/* ------------------------------------------------------------------------------------------------------
  * Multitaper spectral estimation (src/multitaper.jl)
  *   plan    = MTConfig (:5-135): frames of n samples, nfft, `ntapers` tapers (n x ntapers, column-major Float64,
  *             e.g. dpss(n, nw, ntapers)), inverse normalisations r[taper] (fs ./ taper_weights, :127-131)

@@ -25,7 +25,7 @@ export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, td
        DF2TFilter, filtfilt, nextfastfft, optimalfftfiltlength, Comm, welch_channel_mean, welch_reset!, welch_accumulate!,
        welch_finalize, welch_allreduce!, pin!, unpin!, MTConfig, mt_pgram, mt_pgram!, MTSpectrogramConfig, mt_spectrogram,
        mt_spectrogram!, MTCrossSpectraConfig, mt_cross_power_spectra, mt_cross_power_spectra!, MTCoherenceConfig,
-       mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss
+       mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss, unwrap, unwrap!
 
 const lib = get(ENV, "MI355DSP_LIB", joinpath(@__DIR__, "..", "dsp.jl_amd", "libmi355dsp.so"))
 
@@ -448,6 +448,53 @@ function hilbert(x::Union{AbstractVecOrMat{T},DeviceArray{T}}) where {T<:Real}
                          xd.ptr, n, ncolumns(xd), n, mdtype(S), out.ptr, n, C_NULL))
     back(out, x)
 end
+
+# unwrap / unwrap!   unwrap.jl:17-34, the dims::Integer form: accumulate!(unwrap_kernel(range), y, m; dims) as an integer prefix sum on the device.
+# A Julia array unwrapped along d is (inner, len, outer) = (prod(size[1:d-1]), size[d], prod(size[d+1:end])) as it lies in memory: no transposes.
+function unwrap_geometry(inner::Integer, len::Integer, outer::Integer, ::Type{T}; segments::Integer=0) where {T<:Union{Float32,Float64}}
+    route, S, seglen, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_unwrap_geometry_for, lib), Cint, (Int64, Int64, Int64, Cint, Int64, Ref{Cint}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                inner, len, outer, mdtype(T), segments, route, S, seglen, ws))
+    (route=Int(route[]), segments=Int(S[]), seglen=Int(seglen[]), workspace_bytes=Int(ws[]))
+end
+# the host emulation of the device code (same geometry, same operator): what the CPU tests compare with the serial recurrence
+function unwrap_emulate(m::Array{T,N}, d::Integer; range=2T(pi), segments::Integer=0) where {T<:Union{Float32,Float64},N}
+    y = similar(m)
+    GC.@preserve y m check(ccall((:mdsp_unwrap_emulate_host, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Cint, Cdouble, Int64),
+                                 pointer(m), pointer(y), prod(size(m)[1:d-1]), size(m, d), prod(size(m)[d+1:end]), mdtype(T), Float64(T(range)), segments))
+    y
+end
+function unwrap!(y::DeviceArray{T,N}, m::DeviceArray{T,N}; dims=nothing, range=2T(pi), segments::Integer=0, kwargs...) where {T,N}
+    if dims === nothing
+        N != 1 && throw(ArgumentError("`unwrap!`: required keyword parameter dims missing"))
+        dims = 1
+    end
+    if !(dims isa Integer)
+        dims == 1:N && throw(UnsupportedError("unwrap over all dimensions (dims = 1:N, unwrap_nd!) is not accelerated: use DSP.jl's CPU path"))
+        throw(ArgumentError("`unwrap!`: Invalid dims specified: $dims"))
+    end
+    T <: Union{Float32,Float64} || throw(MethodError(unwrap!, (y, m)))
+    size(y) == size(m) || throw(ArgumentError("unwrap!: y and m must have the same size"))
+    1 <= dims <= N || throw(ArgumentError("`unwrap!`: Invalid dims specified: $dims"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_unwrap_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Cint, Cdouble, Int64),
+                h, prod(size(m)[1:dims-1]), size(m, dims), prod(size(m)[dims+1:end]), mdtype(T), Float64(T(range)), segments))
+    try
+        route, S, seglen, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_unwrap_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], route, S, seglen, ws))
+        check(ccall((:mdsp_unwrap_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), h[], m.ptr, y.ptr, C_NULL))
+    finally
+        ccall((:mdsp_unwrap_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+    y
+end
+unwrap!(m::DeviceArray; kwargs...) = unwrap!(m, m; kwargs...)
+unwrap(m::DeviceArray{T,N}; kwargs...) where {T,N} = unwrap!(DeviceArray{T}(size(m)), m; kwargs...)
+unwrap(m::AbstractArray{T}; kwargs...) where {T<:Union{Float32,Float64}} = download(unwrap!(upload(Array(m)); kwargs...))
+function unwrap!(y::AbstractArray{T,N}, m::AbstractArray{T,N}; kwargs...) where {T<:Union{Float32,Float64},N}
+    copyto!(y, unwrap(m; kwargs...))
+end
+unwrap!(m::AbstractArray{T}; kwargs...) where {T<:Union{Float32,Float64}} = unwrap!(m, m; kwargs...)
 
 # ---------------------------------------------------------------------------------------------- periodograms
 # result types   periodograms.jl:262-330, :765-793
