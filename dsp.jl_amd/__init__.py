@@ -9,6 +9,8 @@ from . import _lib
 from ._lib import ArgumentError, DeviceError, DimensionMismatch, DomainError, UnsupportedError, build  # noqa: F401
 from ._lib import ENGINE_AUTO, ENGINE_FUSED, ENGINE_ROCFFT  # noqa: F401
 from .util import nextfastfft, fftintype, fftouttype, fftabs2type  # noqa: F401
+from .util import (rms, rmsfft, meanfreq, finddelay, shiftsignal, shiftsignal_, alignsignals, alignsignals_, pow2db, amp2db, db2pow, db2amp,  # noqa: F401
+                   ReducePlan, ShiftPlan, reduce_geometry, shift_geometry)
 from . import windows, design  # noqa: F401
 from .windows import (hanning, hann, hamming, rect, bartlett, cosine, blackman, kaiser, dpss, dpsseig, tukey, lanczos, triang,  # noqa: F401
                       gaussian, bartlett_hann, blackmanharris, nuttall, flattop)

@@ -19,6 +19,9 @@ F32, F64, C32, C64 = 0, 1, 2, 3
 ENGINE_AUTO, ENGINE_FUSED, ENGINE_ROCFFT = 0, 1, 2
 OLS_FILT, OLS_CONV = 0, 1
 UNWRAP_CONTIGUOUS, UNWRAP_STRIDED = 0, 1
+REDUCE_SUMABS2, REDUCE_SUMABS2_W, REDUCE_ABSARGMAX = 0, 1, 2
+REDUCE_CONTIGUOUS, REDUCE_STRIDED = 0, 1
+SHIFT_AUTO, SHIFT_DISJOINT, SHIFT_HALO, SHIFT_STAGED = 0, 1, 2, 3
 HOST_PINNED = 1
 COMM_ID_BYTES = 128
 
@@ -124,6 +127,18 @@ PROTOTYPES = {
     "mdsp_unwrap_exec": (ci, [vp, vp, vp, vp]),
     "mdsp_unwrap_geometry_for": (ci, [i64, i64, i64, ci, i64, pint, pi64, pi64, pi64]),
     "mdsp_unwrap_emulate_host": (ci, [vp, vp, i64, i64, i64, ci, cd, i64]),
+    "mdsp_reduce_plan_create": (ci, [pvp, i64, i64, i64, ci, ci, cd, i64, i64]),
+    "mdsp_reduce_plan_destroy": (ci, [vp]),
+    "mdsp_reduce_plan_info": (ci, [vp, pint, pi64, pi64, pi64, pi64]),
+    "mdsp_reduce_exec": (ci, [vp, vp, vp, vp]),
+    "mdsp_reduce_geometry_for": (ci, [i64, i64, i64, ci, ci, i64, pint, pi64, pi64, pi64, pi64]),
+    "mdsp_reduce_emulate": (ci, [vp, vp, i64, i64, i64, ci, ci, cd, i64, i64, i64, pi64]),
+    "mdsp_shift_plan_create": (ci, [pvp, i64, i64, i64, ci, i64, ci]),
+    "mdsp_shift_plan_destroy": (ci, [vp]),
+    "mdsp_shift_plan_info": (ci, [vp, pint, pi64, pi64, pi64, pi64]),
+    "mdsp_shift_exec": (ci, [vp, vp, vp, vp]),
+    "mdsp_shift_geometry_for": (ci, [i64, i64, i64, ci, i64, ci, pint, pi64, pi64, pi64, pi64]),
+    "mdsp_shift_emulate": (ci, [vp, vp, i64, i64, i64, i64, ci, ci, pi64]),
     "mdsp_tdfir_state_exec": (ci, [vp, i64, ci, vp, i64, i64, i64, vp, i64, vp, vp]),
     "mdsp_tdfir_state_exec_t": (ci, [vp, i64, ci, ci, vp, i64, i64, i64, vp, i64, vp, vp]),
     "mdsp_extrapolate": (ci, [vp, i64, i64, i64, ci, i64, vp, i64, vp]),

@@ -352,6 +352,69 @@ int mdsp_unwrap_emulate_host(const void* in_host, void* out_host, int64_t inner,
                              int64_t segments);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Deterministic reductions along one dimension (rms, rmsfft, meanfreq, finddelay of src/util.jl:186-220, :336-347).  The array is
+ *   (inner, len, outer) as for unwrap, reduced along len; one result per line, line = i + inner o:
+ *     MDSP_REDUCE_SUMABS2    sum |x|^2; MDSP_F32 / F64 / C32 / C64; result one Float64.  Float32 terms are formed in Float64 (exact products),
+ *                            Float64 terms rounded as abs2 (re*re + im*im, no FMA contraction).
+ *     MDSP_REDUCE_SUMABS2_W  complex bins X_k, k = 0 .. len-1: result two Float64, sum p_k (k step) and sum p_k, with p_k = abs2(X_k)
+ *                            rounded in the element's real type; `step` = fs / len.  No |X|^2 array is written.
+ *     MDSP_REDUCE_ABSARGMAX  a real line and `centre` >= 0: result two Int64, (index, flag).  The larger |x| wins; at equal |x| the index
+ *                            nearer to centre; at equal distance the smaller index.  NaN samples do not compete and set flag = 1; a line
+ *                            without a candidate gives index -1.
+ *   Store, then sum: no atomics, nothing waits for another workgroup; every addition is one Float64 add in the order csrc/reduce_op.h
+ *   defines, so one plan gives the same bits exec after exec and equals the host emulation bit for bit.  `depth` bounds the additions any
+ *   term passes through.  inner == 1: contiguous route (16-byte loads, ragged head and tail by element: any element alignment); inner > 1:
+ *   strided route (a lane per inner index).  segments as for unwrap (0 = auto, > 0 forced, clamped to len); S == 1 is one launch, S > 1 two
+ *   (partials into the plan's workspace, then a finish).  The order of the contiguous route depends on (address / element size) mod
+ *   (16 / element size) of the array -- `phase` of the emulation -- and on nothing else of the address.
+ *   Checks before any launch: sizes < 0, unknown op, a dtype the op does not take, segments < 0, centre < 0: MDSP_ERR_ARGUMENT.  inner or
+ *   outer == 0 succeeds without a launch; len == 0 gives 0 / index -1.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { MDSP_REDUCE_SUMABS2 = 0, MDSP_REDUCE_SUMABS2_W = 1, MDSP_REDUCE_ABSARGMAX = 2 };
+enum { MDSP_REDUCE_CONTIGUOUS = 0, MDSP_REDUCE_STRIDED = 1 };
+typedef struct mdsp_reduce_plan_s* mdsp_reduce_plan;
+int mdsp_reduce_plan_create(mdsp_reduce_plan* plan, int64_t inner, int64_t len, int64_t outer, int op, int dtype, double step, int64_t centre,
+                            int64_t segments);
+int mdsp_reduce_plan_destroy(mdsp_reduce_plan plan);
+int mdsp_reduce_plan_info(mdsp_reduce_plan plan, int* route, int64_t* nsegments, int64_t* seglen, int64_t* depth, int64_t* workspace_bytes);
+/* out_dev: 8 bytes (SUMABS2) or 16 bytes (the other two) per line, 8-byte aligned. */
+int mdsp_reduce_exec(mdsp_reduce_plan plan, const void* in_dev, void* out_dev, void* stream);
+/* Pure host arithmetic, no device needed.  Any output pointer may be NULL. */
+int mdsp_reduce_geometry_for(int64_t inner, int64_t len, int64_t outer, int op, int dtype, int64_t segments, int* route, int64_t* nsegments,
+                             int64_t* seglen, int64_t* depth, int64_t* workspace_bytes);
+/* Host emulation of the device code (no device): the same geometry, operators and lane walks on host arrays.  depth_reached (may be NULL):
+ * the longest chain of additions the run went through. */
+int mdsp_reduce_emulate(const void* in_host, void* out_host, int64_t inner, int64_t len, int64_t outer, int op, int dtype, double step,
+                        int64_t centre, int64_t segments, int64_t phase, int64_t* depth_reached);
+
+/* ------------------------------------------------------------------------------------------------------
+ * shiftsignal / shiftsignal! (src/util.jl:357-395): y[i] = x[i - s] where that exists, else 0, one line of l elements of 4, 8 or 16 bytes
+ *   (moved as words: any element type).  in_place: out is the input.  Routes, chosen at plan creation and reported:
+ *     MDSP_SHIFT_DISJOINT  out of place, or in place with 2 |s| >= l; one launch
+ *     MDSP_SHIFT_HALO      in place, 0 < |s| < l / 2: destination tiles of max(tile, |s|) elements, their halos copied to the workspace
+ *                          first (|s| elements per tile), then a workgroup per tile walking chunks towards its sources; two launches
+ *     MDSP_SHIFT_STAGED    HALO would leave fewer than 256 tiles: the source range goes through the workspace (l - |s| elements); two launches
+ *   tile: 0 = 256 KiB of elements, > 0 forced (tests); route: MDSP_SHIFT_AUTO or a forced route -- DISJOINT where source and destination
+ *   overlap, or HALO out of place or with s == 0, is MDSP_ERR_ARGUMENT.  |s| > l: MDSP_ERR_DOMAIN.  In place with s == 0 and l == 0 succeed
+ *   without a launch.  Why each route is safe in place: csrc/shift_plan.h, DESIGN.md section 4.12.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { MDSP_SHIFT_AUTO = 0, MDSP_SHIFT_DISJOINT = 1, MDSP_SHIFT_HALO = 2, MDSP_SHIFT_STAGED = 3 };
+typedef struct mdsp_shift_plan_s* mdsp_shift_plan;
+int mdsp_shift_plan_create(mdsp_shift_plan* plan, int64_t l, int64_t s, int64_t elem_bytes, int in_place, int64_t tile, int route);
+int mdsp_shift_plan_destroy(mdsp_shift_plan plan);
+int mdsp_shift_plan_info(mdsp_shift_plan plan, int* route, int64_t* tile, int64_t* chunk, int64_t* ntiles, int64_t* workspace_bytes);
+/* out_dev == in_dev exactly when the plan was made in place; any other overlap is MDSP_ERR_ARGUMENT. */
+int mdsp_shift_exec(mdsp_shift_plan plan, const void* in_dev, void* out_dev, void* stream);
+/* Pure host arithmetic, no device needed.  Any output pointer may be NULL. */
+int mdsp_shift_geometry_for(int64_t l, int64_t s, int64_t elem_bytes, int in_place, int64_t tile, int route, int* route_out, int64_t* tile_out,
+                            int64_t* chunk, int64_t* ntiles, int64_t* workspace_bytes);
+/* Host emulation (no device) of the plan's launches, the units of a launch in the order `order` (0 ascending, 1 descending, 2 odd ones
+ * first); out_host == in_host is in place.  violations (may be NULL): reads of a word of the line after it was written, and HALO reads of a
+ * word outside the reader's own tile -- 0 for a correct schedule. */
+int mdsp_shift_emulate(const void* in_host, void* out_host, int64_t l, int64_t s, int64_t elem_bytes, int64_t tile, int route, int order,
+                       int64_t* violations);
+
+/* ------------------------------------------------------------------------------------------------------
  * Multitaper spectral estimation (src/multitaper.jl)
  *   plan    = MTConfig (:5-135): frames of n samples, nfft, `ntapers` tapers (n x ntapers, column-major Float64,
  *             e.g. dpss(n, nw, ntapers)), inverse normalisations r[taper] (fs ./ taper_weights, :127-131)

@@ -25,7 +25,8 @@ export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, td
        DF2TFilter, filtfilt, nextfastfft, optimalfftfiltlength, Comm, welch_channel_mean, welch_reset!, welch_accumulate!,
        welch_finalize, welch_allreduce!, pin!, unpin!, MTConfig, mt_pgram, mt_pgram!, MTSpectrogramConfig, mt_spectrogram,
        mt_spectrogram!, MTCrossSpectraConfig, mt_cross_power_spectra, mt_cross_power_spectra!, MTCoherenceConfig,
-       mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss, unwrap, unwrap!
+       mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss, unwrap, unwrap!,
+       rms, rmsfft, meanfreq, finddelay, shiftsignal, shiftsignal!, alignsignals, alignsignals!, pow2db, amp2db, db2pow, db2amp
 
 const lib = get(ENV, "MI355DSP_LIB", joinpath(@__DIR__, "..", "dsp.jl_amd", "libmi355dsp.so"))
 
@@ -495,6 +496,138 @@ function unwrap!(y::AbstractArray{T,N}, m::AbstractArray{T,N}; kwargs...) where 
     copyto!(y, unwrap(m; kwargs...))
 end
 unwrap!(m::AbstractArray{T}; kwargs...) where {T<:Union{Float32,Float64}} = unwrap!(m, m; kwargs...)
+
+# ---------------------------------------------------------------------------------------------- util.jl:138-220, :316-430
+# COMMON DSP TOOLS and DELAY FINDING UTILITIES: deterministic device reductions (mdsp_reduce_*: store, then sum; Float64 additions in a fixed order)
+# and a zero-filling shift that is correct in place (mdsp_shift_*).
+db2pow(a::Real) = exp10(a / 10)          # :154
+db2amp(a::Real) = exp10(a / 20)          # :162
+pow2db(a::Real) = 10 * log10(a)          # :170
+amp2db(a::Real) = 20 * log10(a)          # :178
+
+const REDUCE_SUMABS2, REDUCE_SUMABS2_W, REDUCE_ABSARGMAX = Cint(0), Cint(1), Cint(2)
+const SHIFT_AUTO, SHIFT_DISJOINT, SHIFT_HALO, SHIFT_STAGED = Cint(0), Cint(1), Cint(2), Cint(3)
+
+function reduce_geometry(inner::Integer, len::Integer, outer::Integer, op::Integer, ::Type{T}; segments::Integer=0) where {T}
+    route, S, seglen, depth, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_reduce_geometry_for, lib), Cint, (Int64, Int64, Int64, Cint, Cint, Int64, Ref{Cint}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                inner, len, outer, op, mdtype(T), segments, route, S, seglen, depth, ws))
+    (route=Int(route[]), segments=Int(S[]), seglen=Int(seglen[]), depth=Int(depth[]), workspace_bytes=Int(ws[]))
+end
+# the host emulation of the device code (same geometry, operators and order of additions): R = Float64 for the sums, Int64 for ABSARGMAX
+function reduce_emulate(x::Array{T}, inner::Integer, len::Integer, outer::Integer, op::Integer; step::Real=0.0, centre::Integer=0, segments::Integer=0,
+                        phase::Integer=0) where {T}
+    words = op == REDUCE_SUMABS2 ? 1 : 2
+    out = op == REDUCE_ABSARGMAX ? zeros(Int64, words, inner * outer) : zeros(Float64, words, inner * outer)
+    reached = Ref{Int64}(0)
+    GC.@preserve x out check(ccall((:mdsp_reduce_emulate, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Cint, Cint, Cdouble, Int64, Int64, Int64, Ref{Int64}),
+                                   pointer(x), pointer(out), inner, len, outer, op, mdtype(T), Float64(step), centre, segments, phase, reached))
+    out, Int(reached[])
+end
+# one plan, one exec: `out` holds 1 (SUMABS2) or 2 eight-byte words per line
+function reduce_exec!(out::DeviceArray, x::DeviceArray{T}, inner::Integer, len::Integer, outer::Integer, op::Integer; step::Real=0.0, centre::Integer=0,
+                      segments::Integer=0) where {T}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_reduce_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Cint, Cint, Cdouble, Int64, Int64),
+                h, inner, len, outer, op, mdtype(T), Float64(step), centre, segments))
+    try
+        route, S, seglen, depth, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_reduce_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], route, S, seglen, depth, ws))
+        check(ccall((:mdsp_reduce_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), h[], x.ptr, out.ptr, C_NULL))
+    finally
+        ccall((:mdsp_reduce_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+    out
+end
+const ReduceTypes = Union{Float32,Float64,ComplexF32,ComplexF64}
+_sumabs2(x::DeviceArray{T}, inner, len, outer) where {T<:ReduceTypes} = download(reduce_exec!(DeviceArray{Float64}((inner * outer,)), x, inner, len, outer, REDUCE_SUMABS2))
+
+# rms(s; dims)   :186-192 (dims = : or one dimension)
+function rms(s::DeviceArray{T,N}; dims=:) where {T<:ReduceTypes,N}
+    R = real(T)
+    if dims === (:)
+        length(s) == 0 && return R(NaN)
+        return R(sqrt(_sumabs2(s, 1, length(s), 1)[1] / length(s)))
+    end
+    dims isa Integer || throw(UnsupportedError("rms over several dimensions is not accelerated: use DSP.jl's CPU path"))
+    1 <= dims <= N || throw(ArgumentError("rms: Invalid dims specified: $dims"))
+    inner, len, outer = prod(size(s)[1:dims-1]), size(s, dims), prod(size(s)[dims+1:end])
+    osz = ntuple(k -> k == dims ? 1 : size(s, k), N)
+    (inner * outer == 0 || len == 0) && return fill(R(NaN), osz)
+    reshape(R.(sqrt.(_sumabs2(s, inner, len, outer) ./ len)), osz)
+end
+rms(s::AbstractArray{T}; kwargs...) where {T<:ReduceTypes} = rms(upload(Array(s)); kwargs...)
+rms(s::AbstractArray{T}; kwargs...) where {T<:Union{Integer,Complex{<:Integer}}} = rms(float.(s); kwargs...)
+# rmsfft(f)   :200
+rmsfft(f::DeviceArray{T}) where {T<:Complex} = length(f) == 0 ? real(T)(NaN) : real(T)(sqrt(_sumabs2(f, 1, length(f), 1)[1]) / length(f))
+rmsfft(f::AbstractArray{T}) where {T<:Complex} = rmsfft(upload(convert(Array{fftouttype(T)}, f)))
+
+# meanfreq(x, fs)   :211-220: one pass over the bins of rfft(x) forms sum(pxx .* freqrg) and sum(pxx); no |X|^2 array is written
+function meanfreq(x::AbstractVector{T}, fs=2π) where {T<:Real}
+    len = length(x)
+    len > 0 || throw(ArgumentError("meanfreq: empty signal"))
+    X = stft(x, len, 0; nfft=len, window=nothing, onesided=true)
+    bins = X isa DeviceArray ? X : upload(vec(Array(X)))
+    R = promote_type(real(eltype(bins)), typeof(fs / len))
+    sums = download(reduce_exec!(DeviceArray{Float64}((2,)), bins, 1, length(bins), 1, REDUCE_SUMABS2_W; step=Float64(fs / len)))
+    R(sums[1] / sums[2])
+end
+
+# finddelay(x, y)   :336-347: xcorr(y, x), then one device arg-max with the reference's tie rules (nearest to length(x), then the smaller index)
+function finddelay(x::AbstractVector{<:Real}, y::AbstractVector{<:Real})
+    (isempty(x) || isempty(y)) && throw(ArgumentError("reducing over an empty collection is not allowed"))
+    s = xcorr(y, x)
+    sd = s isa DeviceArray ? s : upload(convert(Array{fftintype(eltype(s))}, s))
+    centre = length(x) - 1                                     # center_idx = length(x), 0-based
+    rec = download(reduce_exec!(DeviceArray{Int64}((2,)), sd, 1, length(sd), 1, REDUCE_ABSARGMAX; centre=centre))
+    (rec[2] != 0 || rec[1] < 0) && throw(ArgumentError("finddelay: the cross-correlation holds NaN"))
+    centre - Int(rec[1])
+end
+
+function shift_geometry(l::Integer, s::Integer, elem_bytes::Integer, in_place::Bool; tile::Integer=0, route::Integer=SHIFT_AUTO)
+    r, t, c, n, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_shift_geometry_for, lib), Cint, (Int64, Int64, Int64, Cint, Int64, Cint, Ref{Cint}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                l, s, elem_bytes, in_place, tile, route, r, t, c, n, ws))
+    (route=Int(r[]), tile=Int(t[]), chunk=Int(c[]), ntiles=Int(n[]), workspace_bytes=Int(ws[]))
+end
+# the host walk of a plan's launches (units of a launch in three orders): (result, reads that came after a write)
+function shift_emulate(x::Vector{T}, s::Integer; tile::Integer=0, route::Integer=SHIFT_AUTO, order::Integer=0, in_place::Bool=true) where {T}
+    src = copy(x)
+    dst = in_place ? src : similar(x)
+    bad = Ref{Int64}(0)
+    GC.@preserve src dst check(ccall((:mdsp_shift_emulate, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Int64, Cint, Cint, Ref{Int64}),
+                                     pointer(src), pointer(dst), length(x), s, sizeof(T), tile, route, order, bad))
+    dst, Int(bad[])
+end
+function _shift!(y::DeviceArray{T,1}, x::DeviceArray{T,1}, s::Integer; tile::Integer=0, route::Integer=SHIFT_AUTO) where {T}
+    l = length(x)
+    abs(s) > l && throw(DomainError(s, "The absolute value of s must not be greater than the length of x"))      # :359-361
+    sizeof(T) in (4, 8, 16) || throw(UnsupportedError("shiftsignal: elements of $(sizeof(T)) bytes are not accelerated"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_shift_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Cint, Int64, Cint), h, l, s, sizeof(T), x.ptr == y.ptr, tile, route))
+    try
+        r, t, c, n, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_shift_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], r, t, c, n, ws))
+        check(ccall((:mdsp_shift_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), h[], x.ptr, y.ptr, C_NULL))
+    finally
+        ccall((:mdsp_shift_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+    y
+end
+# shiftsignal!(x, s) / shiftsignal(x, s)   :357-395
+shiftsignal!(x::DeviceArray{T,1}, s::Integer; kwargs...) where {T} = _shift!(x, x, s; kwargs...)
+shiftsignal(x::DeviceArray{T,1}, s::Integer; kwargs...) where {T} = _shift!(DeviceArray{T}(size(x)), x, s; kwargs...)
+shiftsignal(x::AbstractVector, s::Integer; kwargs...) = download(shiftsignal!(upload(Array(x)), s; kwargs...))
+shiftsignal!(x::AbstractVector, s::Integer; kwargs...) = copyto!(x, shiftsignal(x, s; kwargs...))
+# alignsignals!(x, y) / alignsignals(x, y)   :404-430
+function alignsignals!(x, y)
+    d = finddelay(x isa DeviceArray ? download(x) : x, y isa DeviceArray ? download(y) : y)
+    shiftsignal!(x, -d), d
+end
+function alignsignals(x, y)
+    d = finddelay(x isa DeviceArray ? download(x) : x, y isa DeviceArray ? download(y) : y)
+    shiftsignal(x, -d), d
+end
 
 # ---------------------------------------------------------------------------------------------- periodograms
 # result types   periodograms.jl:262-330, :765-793
