@@ -18,7 +18,9 @@ from .design import resample_filter, kaiserord  # noqa: F401
 from .dspbase import conv, conv_, conv_separable, xcorr, hilbert, optimalfftfiltlength, os_fft_complexity, SMALL_FILT_CUTOFF  # noqa: F401
 from .dspbase import filt as _filt_ba, filt_ as _filt_ba_
 from .filters import (FIRFilter, fftfilt, fftfilt_, tdfilt, tdfilt_, resample, inputlength, outputlength,  # noqa: F401
-                      filt as _filt_bx, filt_ as _filt_bx_, filt_stateless, DF2TFilter, filtfilt)
+                      filt as _filt_bx, filt_ as _filt_bx_, filt_stateless, DF2TFilter, filtfilt, SosPlan, sos_geometry)
+from .coefficients import (Biquad, SecondOrderSections, ZeroPoleGain, PolynomialRatio, FilterCoefficients, coefb, coefa,  # noqa: F401
+                           filt_stepstate)
 from .multitaper import (MTConfig, MTSpectrogramConfig, MTCrossSpectraConfig, MTCoherenceConfig, CrossPowerSpectra, Coherence,  # noqa: F401
                          coherence, dpss_config, mt_pgram, mt_pgram_, mt_spectrogram, mt_spectrogram_, mt_cross_power_spectra,
                          mt_cross_power_spectra_, mt_coherence, mt_coherence_)
@@ -37,6 +39,7 @@ def filt(*args, **kw):
     ``filt(b, x)``             FIR, FFT overlap-save when length(b) > 66 (Filters/filt.jl:445, :525)
     ``filt(f::FIRFilter, x)``  stateful polyphase filter                 (stream_filt.jl:627)
     ``filt(f::DF2TFilter, x)`` stateful FIR filter (TDF-II state)        (Filters/filt.jl:153)
+    ``filt(f, x)``             ``f`` a Biquad / SecondOrderSections / ZeroPoleGain / PolynomialRatio (Filters/filt.jl:30, :64, :91, :95)
     ``filt(h, x, ratio)``      stateless polyphase filter                (stream_filt.jl:663)
     ``filt(h, x, rate::float, Nphi=32)``  stateless arbitrary-rate resampler (stream_filt.jl:669)
     """

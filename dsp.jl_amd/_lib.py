@@ -127,6 +127,12 @@ PROTOTYPES = {
     "mdsp_unwrap_exec": (ci, [vp, vp, vp, vp]),
     "mdsp_unwrap_geometry_for": (ci, [i64, i64, i64, ci, i64, pint, pi64, pi64, pi64]),
     "mdsp_unwrap_emulate_host": (ci, [vp, vp, i64, i64, i64, ci, cd, i64]),
+    "mdsp_sos_plan_create": (ci, [pvp, pdbl, i64, cd, ci, ci, i64, i64, i64]),
+    "mdsp_sos_plan_destroy": (ci, [vp]),
+    "mdsp_sos_plan_info": (ci, [vp, pi64, pi64, pi64, pi64, pi64]),
+    "mdsp_sos_exec": (ci, [vp, vp, i64, vp, i64, vp, ci, vp]),
+    "mdsp_sos_geometry_for": (ci, [i64, ci, i64, i64, i64, pi64, pi64, pi64, pi64, pi64]),
+    "mdsp_sos_emulate_host": (ci, [vp, i64, vp, i64, vp, pdbl, i64, cd, ci, ci, i64, i64, i64, ci]),
     "mdsp_reduce_plan_create": (ci, [pvp, i64, i64, i64, ci, ci, cd, i64, i64]),
     "mdsp_reduce_plan_destroy": (ci, [vp]),
     "mdsp_reduce_plan_info": (ci, [vp, pint, pi64, pi64, pi64, pi64]),

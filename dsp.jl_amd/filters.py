@@ -9,8 +9,9 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _dev, _lib, _plancache, design, dspbase, util
-from ._lib import ArgumentError, DomainError, UnsupportedError
+from . import _dev, _lib, _plancache, coefficients, design, dspbase, util
+from ._lib import ArgumentError, DimensionMismatch, DomainError, UnsupportedError
+from .coefficients import Biquad, FilterCoefficients, PolynomialRatio, SecondOrderSections, ZeroPoleGain
 from .dspbase import SMALL_FILT_CUTOFF, OlsPlan, _cast_result, _compute_dtype, _host_vec, optimalfftfiltlength
 
 _REAL_KINDS = "fiub"
@@ -95,7 +96,12 @@ def filt(b, x, engine: int = _lib.ENGINE_AUTO):
     length(b) > SMALL_FILT_CUTOFF (66), time domain otherwise.
 
     Complex taps: time domain up to SMALL_FILT_CUTOFF taps, as the reference; longer ones take the complex overlap-save plan, where the
-    reference stays in the time domain (filt.jl:553) -- the results agree to rounding, and the cost does not grow with length(b)."""
+    reference stays in the time domain (filt.jl:553) -- the results agree to rounding, and the cost does not grow with length(b).
+
+    ``filt(f, x)`` with ``f`` a ``Biquad``, ``SecondOrderSections`` or ``ZeroPoleGain`` (converted first, filt.jl:95) is the cascade of second-order
+    sections on the device (filt.jl:35-92); a ``PolynomialRatio`` forwards to ``filt(b, a, x)``."""
+    if isinstance(b, FilterCoefficients):
+        return _filt_coef(b, x)
     bv = _host_vec(b)
     xdt = _dev.np_dtype_of(x)
     if bv.dtype.kind in _REAL_KINDS and xdt.kind in _REAL_KINDS and len(bv) > SMALL_FILT_CUTOFF:
@@ -106,7 +112,15 @@ def filt(b, x, engine: int = _lib.ENGINE_AUTO):
 
 
 def filt_(out, b, x):
-    """``filt!(out, b, x)`` (filt.jl:530-533)."""
+    """``filt!(out, b, x)`` (filt.jl:530-533); ``filt!(out, f, x)`` for coefficient objects (:53-62, :82-89) and for a ``DF2TFilter`` built from one."""
+    if isinstance(b, DF2TFilter):
+        return b.filt_(out, x)
+    if isinstance(b, FilterCoefficients) and not isinstance(b, PolynomialRatio):
+        if tuple(out.shape) != tuple(x.shape):
+            raise DimensionMismatch("out size must match x")              # :54, :83
+        return _assign(out, _filt_coef(b, x))
+    if isinstance(b, PolynomialRatio):
+        return dspbase.filt_(out, b.b, b.a, x)
     if tuple(out.shape) != tuple(x.shape):
         raise ArgumentError("out must be the same size as x")
     return _assign(out, filt(b, x))
@@ -118,6 +132,100 @@ def _assign(out, res):
     else:
         out.copy_(res if not isinstance(res, np.ndarray) else _dev.torch.from_numpy(res))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Biquad / SecondOrderSections on the device   (Filters/filt.jl:35-96)
+# ---------------------------------------------------------------------------------------------------------
+class SosPlan:
+    """``mdsp_sos_plan``: ``segments``, ``seglen``, ``tile``, ``run``, ``workspace_bytes``.  ``coef`` is K x 5 (b0 b1 b2 a1 a2 per section), ``gain`` None for
+    a ``Biquad`` (no gain), ``dtype`` the working type.  ``segments`` = 0 lets the library cut the columns; a positive value forces the cut (tests,
+    tools/sos_bench.py).  Creating a plan needs no device."""
+
+    def __init__(self, coef, gain, dtype, n, ncols, segments=0):
+        self._h = C.c_void_p()
+        self.coef = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 5)
+        self.dtype, self.n, self.ncols = np.dtype(dtype), int(n), int(ncols)
+        _lib.check(_lib.lib().mdsp_sos_plan_create(C.byref(self._h), self.coef.ctypes.data_as(_lib.pdbl), len(self.coef), 1.0 if gain is None else float(gain),
+                                                   0 if gain is None else 1, _dev.md_dtype(self.dtype), self.n, self.ncols, int(segments)))
+        S, seglen, tile, run, ws = (C.c_int64() for _ in range(5))
+        _lib.check(_lib.lib().mdsp_sos_plan_info(self._h, C.byref(S), C.byref(seglen), C.byref(tile), C.byref(run), C.byref(ws)))
+        self.segments, self.seglen, self.tile, self.run, self.workspace_bytes = S.value, seglen.value, tile.value, run.value, ws.value
+
+    def exec(self, x_ptr: int, ldx: int, y_ptr: int, ldy: int, state_ptr: int | None = None, reverse: bool = False, stream: int | None = None):
+        _lib.check(_lib.lib().mdsp_sos_exec(self._h, x_ptr, int(ldx), y_ptr, int(ldy), state_ptr, 1 if reverse else 0,
+                                            _dev.stream_ptr() if stream is None else stream))
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().mdsp_sos_plan_destroy(self._h)
+        except Exception:
+            pass
+
+
+def sos_geometry(nsections: int, dtype, n: int, ncols: int, segments: int = 0):
+    """(segments, seglen, tile, run, workspace_bytes) a plan for these arguments has: host arithmetic of the library, no device needed."""
+    S, seglen, tile, run, ws = (C.c_int64() for _ in range(5))
+    _lib.check(_lib.lib().mdsp_sos_geometry_for(int(nsections), _dev.md_dtype(dtype), int(n), int(ncols), int(segments),
+                                                C.byref(S), C.byref(seglen), C.byref(tile), C.byref(run), C.byref(ws)))
+    return S.value, seglen.value, tile.value, run.value, ws.value
+
+
+def _as_sections(f):
+    """(K x 5 table, gain or None, coefficient eltype, gain eltype or None) of a Biquad / SecondOrderSections / ZeroPoleGain."""
+    if isinstance(f, Biquad):
+        return np.array([[float(v) for v in f.coefficients()]]), None, f.dtype, None
+    if not isinstance(f, SecondOrderSections):
+        f = SecondOrderSections(f)                                      # filt.jl:95-96
+    if not f.biquads:
+        raise ArgumentError("a SecondOrderSections filter needs at least one section")
+    return f.table(), f.g, f.dtype, f.gdtype
+
+
+_validated: set = set()
+
+
+def _validate_sections(table, gain, W):
+    """The library's own checks of a cascade (section count, finite coefficients, stability) on the host, before anything touches a device: a plan for
+    an empty signal is created and dropped.  Remembered per cascade and working type."""
+    key = (table.tobytes(), None if gain is None else float(gain), np.dtype(W).str)
+    if key not in _validated:
+        SosPlan(table, gain, W, 0, 0)
+        if len(_validated) > 256:
+            _validated.clear()
+        _validated.add(key)
+
+
+def _sos_exec(table, gain, W, cols, out, state=None, reverse=False):
+    """One pass of the cascade over the (ncols, n) device columns ``cols`` into ``out`` (may be ``cols``); ``state``: (ncols, K, 2) of W, updated."""
+    ncols, n = cols.shape
+    if n == 0 or ncols == 0:
+        return
+    key = ("sos", _plancache.ctx_key(), table.tobytes(), None if gain is None else float(gain), np.dtype(W).str, n, ncols)
+    plan = _plancache.plans.get(key, lambda: SosPlan(table, gain, W, n, ncols))
+    plan.exec(_dev.ptr(cols), n, _dev.ptr(out), n, None if state is None else _dev.ptr(state), reverse)
+
+
+def _own_columns(x, W):
+    """``_dev.to_columns`` plus the buffer the result goes to: the columns themselves when they are a copy of our own (filtered in place), a fresh buffer
+    when they are the caller's memory (a device vector already of type W)."""
+    cols, shape = _dev.to_columns(x, W)
+    if _dev.is_device_array(x) and cols.numel() and cols.data_ptr() == x.data_ptr():
+        return cols, _dev.empty_columns(cols.shape[0], cols.shape[1], W), shape
+    return cols, cols, shape
+
+
+def _filt_coef(f, x):
+    """``filt(f, x)`` for Biquad / SecondOrderSections / ZeroPoleGain (filt.jl:64-65, :91-92, :95); PolynomialRatio: ``filt(b, a, x)`` (:30)."""
+    if isinstance(f, PolynomialRatio):
+        return dspbase.filt(f.b, f.a, x)
+    table, gain, T, G = _as_sections(f)
+    W = _compute_dtype(util.promote_type(T, _dev.np_dtype_of(x), *(() if G is None else (G,))))
+    _validate_sections(table, gain, W)
+    cols, out, shape = _own_columns(x, W)
+    _sos_exec(table, gain, W, cols, out)
+    return _dev.from_columns(out, shape, x)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -456,6 +564,19 @@ class DF2TFilter:
     left to DSP.jl's CPU code (``UnsupportedError``)."""
 
     def __init__(self, b, a=1.0, dtype=None, coldims=()):
+        self._sections = None
+        if isinstance(b, PolynomialRatio):                              # DF2TFilter(coef::PolynomialRatio, ...): the vector form below
+            b, a = b.b, b.a
+        elif isinstance(b, FilterCoefficients):                         # filt.jl:184-186, :198-200, :227-230
+            self.coef = b if isinstance(b, (Biquad, SecondOrderSections)) else SecondOrderSections(b)
+            table, gain, T, G = _as_sections(self.coef)
+            self._sections = (table, gain)
+            S = util.promote_type(T, *(() if G is None else (G,)), *(() if dtype is None else (dtype,)))   # zeros(promote_type(T, G, V), 2, K, coldims...)
+            self._T = _compute_dtype(S)
+            _validate_sections(table, gain, self._T)
+            lead = (2,) if isinstance(self.coef, Biquad) else (2, len(table))
+            self.state = _dev.torch.zeros(lead + tuple(int(k) for k in coldims), dtype=_dev.torch_dtype(self._T), device=_dev.device())
+            return
         bv, av = _host_vec(b), _host_vec(a)
         if bv.size == 0 or av.size == 0:
             raise ArgumentError("filter coefficients must be non-empty")
@@ -475,6 +596,8 @@ class DF2TFilter:
 
     def filt(self, x):
         """``filt(f, x)`` = ``filt!(similar(x, promote_type(...)), f, x)`` (filt.jl:153-181)."""
+        if self._sections is not None:
+            return self._filt_sections(x)
         if tuple(x.shape[1:]) != tuple(self.state.shape[1:]):
             raise ArgumentError("state size must match x")              # :158
         xdt = _dev.np_dtype_of(x)
@@ -501,10 +624,63 @@ class DF2TFilter:
             self.state = si.t().reshape(self.state.shape).contiguous()
         return _dev.from_columns(out, shape, x)
 
+    def _filt_sections(self, x):
+        """``filt(f::DF2TFilter{<:SecondOrderSections}, x)`` / ``{<:Biquad}`` (filt.jl:188-210, :223-224): the state is carried from call to call."""
+        table, gain = self._sections
+        if tuple(x.shape[1:]) != tuple(self.state.shape[1 if isinstance(self.coef, Biquad) else 2:]):
+            raise ArgumentError("state size must match x")                  # :190, :205
+        W = _compute_dtype(util.promote_type(self._T, _dev.np_dtype_of(x)))
+        if self._T != W:                                                    # a wider signal eltype widens the state for good
+            self.state = self.state.to(_dev.torch_dtype(W))
+            self._T = W
+        cols, out, shape = _own_columns(x, W)
+        ncols, nx = cols.shape
+        if nx and ncols:
+            K = len(table)
+            si = self.state.reshape(2, K, ncols).permute(2, 1, 0).contiguous()     # (ncols, K, 2): element s + 2 (k + K c), what the library takes
+            _sos_exec(table, gain, W, cols, out, si)
+            self.state = si.permute(2, 1, 0).reshape(self.state.shape).contiguous()
+        return _dev.from_columns(out, shape, x)
+
+    def filt_(self, out, x):
+        """``filt!(out, f::DF2TFilter, x)``."""
+        if tuple(out.shape) != tuple(x.shape):
+            raise ArgumentError("out size must match x")                    # :154, :189, :203
+        return _assign(out, self.filt(x))
+
+
+def _filtfilt_sections(f, x):
+    """``filtfilt(f::SecondOrderSections, x)`` (filt.jl:341-360): step-state start, odd extension by min(6K, n - 1) samples, a forward pass and a pass from
+    the last sample to the first (the library's ``reverse`` walk instead of two flips), trim.  A Biquad runs as its one-section cascade."""
+    sos = f if isinstance(f, SecondOrderSections) else SecondOrderSections(f)
+    table, gain, T, G = _as_sections(sos)
+    K = len(table)
+    n = int(x.shape[0])
+    W = _compute_dtype(util.promote_type(T, G, _dev.np_dtype_of(x)))
+    _validate_sections(table, gain, W)
+    cols, shape = _dev.to_columns(x, W)
+    ncols = cols.shape[0]
+    if n == 0 or ncols == 0:
+        return _dev.from_columns(_dev.empty_columns(ncols, n, W), shape, x)
+    zi = coefficients.filt_stepstate(sos)                               # (2, K) in T, :342
+    pad = min(6 * K, n - 1)                                             # :343
+    ext = _dev.empty_columns(ncols, n + 2 * pad, W)
+    _lib.check(_lib.lib().mdsp_extrapolate(_dev.ptr(cols), n, ncols, n, _dev.md_dtype(W), pad, _dev.ptr(ext), n + 2 * pad, _dev.stream_ptr()))
+    zit = _dev.torch.from_numpy(np.ascontiguousarray(zi.T)).to(device=ext.device, dtype=ext.dtype)     # (K, 2)
+    state = (zit[None, :, :] * ext[:, 0][:, None, None]).contiguous()   # mul!(zitmp, zi, extrapolated[1]), :351
+    _sos_exec(table, gain, W, ext, ext, state)
+    state = (zit[None, :, :] * ext[:, -1][:, None, None]).contiguous()  # after reverse!: the last filtered sample, :353
+    _sos_exec(table, gain, W, ext, ext, state, reverse=True)
+    return _dev.from_columns(ext[:, pad:pad + n], shape, x)             # out[j] = extrapolated[end - pad_length + 1 - j] of the reversed vector, :355
+
 
 def filtfilt(b, *args):
     """``filtfilt(b, x)`` / ``filtfilt(b, a, x)`` with scalar or length-1 ``a`` (filt.jl:301-338): zero-phase FIR
     filtering -- odd-symmetric extension by ``length(b)-1`` samples, one pass with ``conv(b, reverse(b))``, trim.  ``b`` real or complex."""
+    if isinstance(b, FilterCoefficients) and len(args) == 1:
+        if isinstance(b, PolynomialRatio):                              # filt.jl:364
+            return filtfilt(b.b, b.a, args[0])
+        return _filtfilt_sections(b, args[0])                           # :341, :363
     if len(args) == 2:
         a, x = args
         av = _host_vec(a)

@@ -352,6 +352,41 @@ int mdsp_unwrap_emulate_host(const void* in_host, void* out_host, int64_t inner,
                              int64_t segments);
 
 /* ------------------------------------------------------------------------------------------------------
+ * filt / filt! for Biquad and SecondOrderSections (Filters/filt.jl:35-92), the stateful DF2TFilter forms (:188-210) and the two passes of
+ * filtfilt (:341-360): a cascade of K second-order sections along the first dimension of n x ncols columns, ld elements apart.
+ *   coef: K x 5 doubles, b0 b1 b2 a1 a2 per section (a0 = 1), rounded to the working type's real type before anything else.  has_gain != 0:
+ *   the output of the last section is multiplied by gain (SecondOrderSections); has_gain == 0: it is the output (Biquad).
+ *   dtype is the WORKING type promote_type(T, G, S) of the reference: MDSP_F32 / F64, or MDSP_C32 / C64 for a complex signal, whose columns
+ *   are filtered as two real lines of element stride 2 (the coefficients are real).  x, y and state are arrays of that type.
+ *   Per sample and section: y = fma(b0, x, s1); s1 = fma(a1, -y, fma(b1, x, s2)); s2 = fma(b2, x, -a2 * y), every operation rounded once in the
+ *   working type.  Given the state at its first sample, every run of 16 samples is computed by exactly this serial recurrence; a scan with
+ *   powers of the cascade's 2K x 2K state matrix (host, long double, rounded once) supplies the start states (csrc/sos_scan.h).
+ *   state_dev: (2, K, ncols) values of the working type, element s + 2 (k + K c): read as the state in front of the first sample, overwritten with
+ *   the state behind the last; NULL: zero state, end state dropped.  reverse != 0 walks every column from its last sample to its first (reads
+ *   x[n-1-i], writes y[n-1-i]).  y_dev == x_dev with ldy == ldx filters in place; any other overlap is MDSP_ERR_ARGUMENT.
+ *   segments as for unwrap: 0 = automatic, > 0 forced (clamped to n); S == 1 is one launch, S > 1 three (end states, carries, apply) with
+ *   2 K values of workspace per segment and line.  tile = 64 run samples.  No atomics, nothing waits: results depend on the arguments only
+ *   and equal mdsp_sos_emulate_host bit for bit.
+ *   Checks, before any launch: negative sizes, nsections < 1, a bad dtype, non-finite coefficients or gain, ld < n, a partial overlap:
+ *   MDSP_ERR_ARGUMENT.  nsections > 16, a section with a pole of modulus above 1 (its carry matrices grow without bound; poles ON the unit
+ *   circle run), or carry matrices that overflow the working type: MDSP_ERR_UNSUPPORTED.  n == 0 or ncols == 0 succeeds without a launch.
+ *   A plan touches the device at its first exec, not at creation: that call allocates and copies the carry matrices with a blocking hipMemcpy, so
+ *   a plan's FIRST exec must not be inside a stream capture (later ones only launch kernels).
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct mdsp_sos_plan_s* mdsp_sos_plan;
+int mdsp_sos_plan_create(mdsp_sos_plan* plan, const double* coef, int64_t nsections, double gain, int has_gain, int dtype, int64_t n, int64_t ncols,
+                         int64_t segments);
+int mdsp_sos_plan_destroy(mdsp_sos_plan plan);
+int mdsp_sos_plan_info(mdsp_sos_plan plan, int64_t* nsegments, int64_t* seglen, int64_t* tile, int64_t* run, int64_t* workspace_bytes);
+int mdsp_sos_exec(mdsp_sos_plan plan, const void* x_dev, int64_t ldx, void* y_dev, int64_t ldy, void* state_dev, int reverse, void* stream);
+/* Pure host arithmetic, no device needed.  Any output pointer may be NULL. */
+int mdsp_sos_geometry_for(int64_t nsections, int dtype, int64_t n, int64_t ncols, int64_t segments, int64_t* nsegments, int64_t* seglen,
+                          int64_t* tile, int64_t* run, int64_t* workspace_bytes);
+/* Host emulation of the device code (no device): the same cut, tiles, scan order and arithmetic (csrc/sos_scan.h) on host arrays. */
+int mdsp_sos_emulate_host(const void* x_host, int64_t ldx, void* y_host, int64_t ldy, void* state_host, const double* coef, int64_t nsections,
+                          double gain, int has_gain, int dtype, int64_t n, int64_t ncols, int64_t segments, int reverse);
+
+/* ------------------------------------------------------------------------------------------------------
  * Deterministic reductions along one dimension (rms, rmsfft, meanfreq, finddelay of src/util.jl:186-220, :336-347).  The array is
  *   (inner, len, outer) as for unwrap, reduced along len; one result per line, line = i + inner o:
  *     MDSP_REDUCE_SUMABS2    sum |x|^2; MDSP_F32 / F64 / C32 / C64; result one Float64.  Float32 terms are formed in Float64 (exact products),

@@ -25,7 +25,7 @@ export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, td
        DF2TFilter, filtfilt, nextfastfft, optimalfftfiltlength, Comm, welch_channel_mean, welch_reset!, welch_accumulate!,
        welch_finalize, welch_allreduce!, pin!, unpin!, MTConfig, mt_pgram, mt_pgram!, MTSpectrogramConfig, mt_spectrogram,
        mt_spectrogram!, MTCrossSpectraConfig, mt_cross_power_spectra, mt_cross_power_spectra!, MTCoherenceConfig,
-       mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss, unwrap, unwrap!,
+       mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss, unwrap, unwrap!, sosfilt, sosfilt!,
        rms, rmsfft, meanfreq, finddelay, shiftsignal, shiftsignal!, alignsignals, alignsignals!, pow2db, amp2db, db2pow, db2amp
 
 const lib = get(ENV, "MI355DSP_LIB", joinpath(@__DIR__, "..", "dsp.jl_amd", "libmi355dsp.so"))
@@ -496,6 +496,53 @@ function unwrap!(y::AbstractArray{T,N}, m::AbstractArray{T,N}; kwargs...) where 
     copyto!(y, unwrap(m; kwargs...))
 end
 unwrap!(m::AbstractArray{T}; kwargs...) where {T<:Union{Float32,Float64}} = unwrap!(m, m; kwargs...)
+
+# Biquad / SecondOrderSections   Filters/filt.jl:35-96, :188-210, :341-360: the cascade of second-order sections on the device (mdsp_sos_*).
+# coef is 5 x K (b0 b1 b2 a1 a2 down each column, a0 = 1: the K x 5 rows the C ABI takes, as they lie in memory), gain === nothing for a Biquad.
+# From DSP.jl's types: coef = [getfield(q, f) for f in (:b0, :b1, :b2, :a1, :a2), q in f.biquads], gain = f.g.  T is the working type
+# promote_type(T, G, S); a complex signal runs as two real lines per column.
+const SosTypes = Union{Float32,Float64,ComplexF32,ComplexF64}
+function sos_geometry(K::Integer, ::Type{T}, n::Integer, ncols::Integer; segments::Integer=0) where {T<:SosTypes}
+    S, seglen, tile, run, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_sos_geometry_for, lib), Cint, (Int64, Cint, Int64, Int64, Int64, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                K, mdtype(T), n, ncols, segments, S, seglen, tile, run, ws))
+    (segments=Int(S[]), seglen=Int(seglen[]), tile=Int(tile[]), run=Int(run[]), workspace_bytes=Int(ws[]))
+end
+# the host emulation of the device code (same cut, tiles, scan order and arithmetic): equal to the device bit for bit.  state: (2, K, ncols) or nothing
+function sos_emulate(coef::Matrix{Float64}, gain::Union{Nothing,Real}, x::Array{T}; state::Union{Nothing,Array{T}}=nothing, reverse::Bool=false,
+                     segments::Integer=0) where {T<:SosTypes}
+    size(coef, 1) == 5 || throw(ArgumentError("coef must be 5 x K"))
+    y = similar(x)
+    n, ncols = size(x, 1), div(length(x), max(size(x, 1), 1))
+    GC.@preserve x y state coef check(ccall((:mdsp_sos_emulate_host, lib), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cdouble}, Int64, Cdouble, Cint, Cint, Int64, Int64, Int64, Cint),
+        pointer(x), n, pointer(y), n, state === nothing ? C_NULL : pointer(state), pointer(coef), size(coef, 2), gain === nothing ? 1.0 : Float64(gain),
+        gain === nothing ? 0 : 1, mdtype(T), n, ncols, segments, reverse ? 1 : 0))
+    y
+end
+# filt!(y, f, x) on device columns; y === x filters in place.  state: a (2, K, ncols) DeviceArray{T}, read as the state in front of the first sample and
+# overwritten with the state behind the last (the DF2TFilter forms), or nothing (zero state, end state dropped).  reverse: the backward pass of filtfilt.
+function sosfilt!(y::DeviceArray{T}, coef::Matrix{Float64}, gain::Union{Nothing,Real}, x::DeviceArray{T}; state::Union{Nothing,DeviceArray{T}}=nothing,
+                  reverse::Bool=false, segments::Integer=0) where {T<:SosTypes}
+    size(coef, 1) == 5 || throw(ArgumentError("coef must be 5 x K"))
+    size(x) == size(y) || throw(DimensionMismatch("out size must match x"))                                    # filt.jl:54
+    K, n, ncols = size(coef, 2), size(x, 1), ncolumns(x)
+    state === nothing || size(state)[1:2] == (2, K) && div(length(state), 2K) == ncols || throw(ArgumentError("state size must match x"))   # :190
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve coef check(ccall((:mdsp_sos_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Ptr{Cdouble}, Int64, Cdouble, Cint, Cint, Int64, Int64, Int64),
+                                  h, pointer(coef), K, gain === nothing ? 1.0 : Float64(gain), gain === nothing ? 0 : 1, mdtype(T), n, ncols, segments))
+    try
+        S, seglen, tile, run, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_sos_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], S, seglen, tile, run, ws))
+        check(ccall((:mdsp_sos_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}),
+                    h[], x.ptr, n, y.ptr, n, state === nothing ? C_NULL : state.ptr, reverse ? 1 : 0, C_NULL))
+    finally
+        ccall((:mdsp_sos_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+    y
+end
+sosfilt(coef::Matrix{Float64}, gain, x::DeviceArray{T}; kwargs...) where {T<:SosTypes} = sosfilt!(DeviceArray{T}(size(x)), coef, gain, x; kwargs...)
+sosfilt(coef::Matrix{Float64}, gain, x::AbstractArray{T}; kwargs...) where {T<:SosTypes} = download(sosfilt!(upload(Array(x)), coef, gain, upload(Array(x)); kwargs...))
 
 # ---------------------------------------------------------------------------------------------- util.jl:138-220, :316-430
 # COMMON DSP TOOLS and DELAY FINDING UTILITIES: deterministic device reductions (mdsp_reduce_*: store, then sum; Float64 additions in a fixed order)
