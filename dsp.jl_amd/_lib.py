@@ -83,6 +83,7 @@ PROTOTYPES = {
     "mdsp_ols_plan_tile": (ci, [vp, pi64, pi64]),
     "mdsp_ols_tile_for": (ci, [i64, i64, i64, ci, ci, ci, pi64, pi64]),
     "mdsp_ols_stream_for": (ci, [i64, i64, i64, ci, pint]),
+    "mdsp_ols_run_for": (ci, [i64, i64, ci, pi64, pi64]),
     "mdsp_ols_exec_range": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, i64, vp]),
     "mdsp_ols_exec_host": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, ci]),
     "mdsp_ols_segment": (ci, [vp, vp, i64, i64, i64, vp, vp]),

@@ -127,6 +127,7 @@ static const KnobDef kKnobs[] = {
     {"MDSP_OLS_PREFETCH", &Tunables::ols_prefetch, 0, 0, 1},
     {"MDSP_OLS_TILE", &Tunables::ols_tile, 1, 0, 1},
     {"MDSP_OLS_STREAM", &Tunables::ols_stream, 1, 0, 2},
+    {"MDSP_OLS_RUN_LEN", &Tunables::ols_run_len, 0, 0, 1 << 20},
     {"MDSP_GEN_WIDE", &Tunables::gen_wide, 1, 0, 1},
     {"MDSP_GEN_CT_F64_MAX", &Tunables::gen_ct_f64_max, 8000, 0, 1 << 20},
     {"MDSP_BIG_GROUPS", &Tunables::big_groups, 0, 0, 1 << 20},

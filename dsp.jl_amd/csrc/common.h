@@ -169,7 +169,9 @@ struct Tunables {
     int ols_tile = 1;                   // MDSP_OLS_TILE=0          : no tiled overlap-save plans (ols_plan.h): every plan runs windows of L outputs with nb - 1 samples of lead
     int ols_stream = 1;                 // MDSP_OLS_STREAM=0|1|2    : streaming cache policy of the tiled overlap-save kernel (ols_plan.h ols_stream_rule), read at launch: 0 = never,
                                         //                            1 = by the footprint rule (launches that touch more than 512 MiB; the default), 2 = every tiled launch (tests, A/B)
-    int ols_prefetch = 0;               // MDSP_OLS_PREFETCH=1      : overlap-save kernel with software prefetch of the next unit (default: off)
+    int ols_run_len = 0;                // MDSP_OLS_RUN_LEN         : units per run of the fused overlap-save kernel's slots (ols_plan.h ols_run_len), read at launch: 0 = the run rule
+                                        //                            (the default), n > 0 = runs of n units for every fused launch (tests, A/B); MDSP_RUNS_PER_SLOT != 1 wins
+    int ols_prefetch = 0;              // MDSP_OLS_PREFETCH=1      : overlap-save kernel with software prefetch of the next unit (default: off)
     int gx = 1;                         // MDSP_GX=0|2              : 0 = no run-time-schedule single-workgroup kernel (spectral_gx.h: sizes without a compile-time schedule go to
                                         //                            the round-2 LDS kernel / the multi-pass engine / rocFFT as up to round 5); 2 = that kernel for EVERY size it plans (A/B); 6 = no rows above 8192 points (spectral_ctcols_big.hip); 4 = never the compile-time kernels of spectral_ctcols.hip / spectral_ctbig.hip, 5 = never spectral_ctbig.hip (A/B)
     int bigfft = 1;                     // MDSP_BIGFFT=0            : transforms above the one-workgroup sizes go to the rocFFT pipeline instead of the multi-pass fused engine (bigfft.hip)

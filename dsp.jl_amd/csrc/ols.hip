@@ -816,10 +816,11 @@ int launch_fused_geo(const OlsFusedArgs& a, hipStream_t s) {
     const int64_t want = cdiv(todo, G);
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)device_cu_count() * per_cu));
     OlsFusedArgs b = a;
-    const int64_t runs = tunables().runs_per_slot;                     // runs per slot (1 = fully contiguous)
     const int64_t nslots = (int64_t)grid * G;
-    b.run_len = std::max<int64_t>(1, cdiv(todo, nslots * runs));
-    b.niter = cdiv(cdiv(todo, b.run_len), nslots) * b.run_len;
+    // the run schedule (ols_plan.h): short cyclic runs for the streaming tiled instantiations, one contiguous run per slot for every other one
+    constexpr bool STREAMING = TILED && (AUXL != MDSP_IO_AUX_LOAD || AUXS != MDSP_IO_AUX_STORE);
+    b.run_len = mdsp::ols_run_len(todo, nslots, STREAMING, tunables().runs_per_slot, tunables().ols_run_len);
+    b.niter = mdsp::ols_run_niter(todo, nslots, b.run_len);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), 0, s, b);
     MDSP_LAUNCH_CHECK();
     return MDSP_OK;
@@ -1175,6 +1176,15 @@ int mdsp_ols_stream_for(int64_t nx, int64_t nout, int64_t columns, int dtype, in
     if (nx < 0 || nout < 0 || columns < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "negative size");
     const bool can_tile = dtype == MDSP_F32 && tunables().ols_tile == 1;
     if (streaming) *streaming = mdsp::ols_stream_rule(tunables().ols_stream, can_tile, nx, nout, columns, (int64_t)dtype_size(dtype)) ? 1 : 0;
+    return MDSP_OK;
+}
+
+// The run schedule (ols_plan.h) launch_fused_geo gives a launch of `units` units on `slots` slots, under the knobs as they stand.
+int mdsp_ols_run_for(int64_t units, int64_t slots, int streaming_tiled, int64_t* run_len, int64_t* niter) {
+    if (units < 0 || slots < 1) MDSP_FAIL(MDSP_ERR_ARGUMENT, "units (%lld) must be >= 0 and slots (%lld) >= 1", (long long)units, (long long)slots);
+    const int64_t rl = mdsp::ols_run_len(units, slots, streaming_tiled != 0, tunables().runs_per_slot, tunables().ols_run_len);
+    if (run_len) *run_len = rl;
+    if (niter) *niter = mdsp::ols_run_niter(units, slots, rl);
     return MDSP_OK;
 }
 

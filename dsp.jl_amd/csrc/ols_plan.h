@@ -41,6 +41,32 @@ inline bool ols_stream_rule(int knob, bool tiled, int64_t nread, int64_t nwritte
     return (nread + nwritten) * columns * elem_bytes > kOlsStreamBytes;
 }
 
+// The run schedule of the fused kernel's persistent grid (DESIGN 4.2 *Run schedule*; ols.hip launch_fused_geo).  Slot s of `nslots` walks runs of run_len
+// consecutive units, run r of slot s at unit (r nslots + s) run_len, every slot the same niter = rounds x run_len iterations (barriers inside).  "Whole"
+// is one run per slot, run_len = ceil(units / nslots): every workgroup streams one contiguous piece, the chunked pattern of a copy.  Short runs keep all
+// slots inside one moving window of nslots x run_len units, the interleaved pattern.  ols_run_rule answers kOlsRunUnits for the streaming tiled launch
+// (`streaming_tiled`: ols_stream_rule said yes) of at least kOlsRunFromUnits units and whole for every other one -- smaller streaming launches, plain
+// tiled, untiled, block ranges, the rows form, Float64, complex --, which keep the schedule they had.  Never longer than whole, never shorter than 1.
+// Measured at 2^30 samples (profiles/ols_runs_ab.json): the memory side alone 1.673 ms whole, 1.617 / 1.599 / 1.614 / 1.634 / 1.655 ms at runs of
+// 1 / 2 / 4 / 8 / 16 units, each below whole in all six rounds, 32 and 73 above it; 2 below 1 and 4 in every round.  The line: runs of 2 lost no round
+// against whole at 2^28 and 2^30 samples (74899 and 299594 units); at 2^27 (37450 units, 37 per slot, where the one iteration more is 2.7 %) they are
+// 5 % faster once the chip is warm and 3 % slower in the first rounds of a process that starts there -- so the smallest power of two above it.
+// Padding: ceil(ceil(units / run_len) / nslots) == ceil(units / (run_len nslots)), so niter is the smallest multiple of run_len that is >= whole:
+// at most run_len - 1 iterations more than whole's, none at run_len == 1; a slot idles through at most one run (the last round's), as with whole.
+// `forced` (knob MDSP_OLS_RUN_LEN, tests and the A/B): > 0 this length for every fused launch; `runs_per_slot` (knob MDSP_RUNS_PER_SLOT) != 1 wins over both.
+constexpr int64_t kOlsRunUnits = 2, kOlsRunFromUnits = int64_t(1) << 16;
+inline int64_t ols_run_whole(int64_t units, int64_t nslots) { return std::max<int64_t>(1, cdiv(units, std::max<int64_t>(1, nslots))); }
+inline int64_t ols_run_rule(int64_t units, int64_t nslots, bool streaming_tiled) {
+    const int64_t whole = ols_run_whole(units, nslots);
+    return streaming_tiled && units >= kOlsRunFromUnits ? std::min(whole, kOlsRunUnits) : whole;
+}
+inline int64_t ols_run_len(int64_t units, int64_t nslots, bool streaming_tiled, int runs_per_slot, int forced) {
+    if (runs_per_slot != 1) return std::max<int64_t>(1, cdiv(units, std::max<int64_t>(1, nslots) * runs_per_slot));
+    if (forced > 0) return std::min<int64_t>(forced, ols_run_whole(units, nslots));
+    return ols_run_rule(units, nslots, streaming_tiled);
+}
+inline int64_t ols_run_niter(int64_t units, int64_t nslots, int64_t run_len) { return cdiv(cdiv(units, run_len), std::max<int64_t>(1, nslots)) * run_len; }
+
 // Tiles [first_tile, first_tile + ntiles) of the grid the whole-column call runs for one column of nx samples / nout outputs, from a slice of the signal:
 // xs_dev holds x[xs_first .. xs_first + xs_len) and covers [first_tile tile - tile_lead, (first_tile + ntiles) tile) clipped to [0, nx); ys_dev[0..] receives
 // the outputs from first_tile tile on.  first_tile even for real dtypes on single-block plans.  Bit-identical to the whole-column call (mdsp_ols_exec_host).

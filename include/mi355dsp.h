@@ -141,6 +141,12 @@ int mdsp_ols_tile_for(int64_t nb, int64_t nfft, int64_t nx_hint, int dtype, int 
  * 1 = the footprint rule (the default) -- launches that read and write more than 512 MiB, (nx + nout) columns 4 bytes, which nothing can still hold in
  * cache for a consumer --, 0 = never, 2 = every launch of a tiled plan.  Always 0 for dtypes that have no tiled plans and under MDSP_OLS_TILE = 0.  No device. */
 int mdsp_ols_stream_for(int64_t nx, int64_t nout, int64_t columns, int dtype, int* streaming);
+/* The run schedule of the fused kernel's persistent grid: a launch of `units` units (pairs of real blocks, complex blocks) on `slots`
+ * transform slots gives every slot runs of *run_len consecutive units, run r of slot s at unit (r slots + s) run_len, and *niter iterations in all (the
+ * same for every slot).  streaming_tiled != 0: the streaming launch of a tiled plan, which walks runs of 2 units from 65536 units on; every other launch walks
+ * one run per slot, *run_len = ceil(units / slots).  Outputs are bit-identical under every schedule.  Knobs (mdsp_set_knob, read at launch): MDSP_OLS_RUN_LEN = n > 0 forces
+ * runs of n units (never longer than one run per slot), MDSP_RUNS_PER_SLOT != 1 that many runs per slot.  No device. */
+int mdsp_ols_run_for(int64_t units, int64_t slots, int streaming_tiled, int64_t* run_len, int64_t* niter);
 /* x_dev: (nx, ncols) ld ldx;  y_dev: (nout, ncols) ld ldy.  nout = nx (filt), nx+nb-1 (conv), or any
  * 0 <= nout <= nx+nb-1.  x and y must not alias (Filters/filt.jl:438-439). */
 int mdsp_ols_exec(mdsp_ols_plan plan, const void* x_dev, int64_t nx, int64_t ncols, int64_t ldx, void* y_dev,

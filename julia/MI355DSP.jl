@@ -260,6 +260,12 @@ function ols_stream_for(nx::Integer, nout::Integer, columns::Integer, ::Type{T})
     check(ccall((:mdsp_ols_stream_for, lib), Cint, (Int64, Int64, Int64, Cint, Ref{Cint}), nx, nout, columns, mdtype(T), streaming))
     streaming[] != 0
 end
+# the run schedule of a fused overlap-save launch of `units` units on `slots` slots (short runs for the streaming tiled launch, else one run per slot)
+function ols_run_for(units::Integer, slots::Integer, streaming_tiled::Bool)
+    run_len, niter = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_ols_run_for, lib), Cint, (Int64, Int64, Cint, Ref{Int64}, Ref{Int64}), units, slots, streaming_tiled ? 1 : 0, run_len, niter))
+    (run_len = Int(run_len[]), niter = Int(niter[]))
+end
 
 # The function-style entry points build a plan per call in the reference (cheap FFTW plans); here the plan comes from the LIBRARY's LRU
 # (mdsp_ols_plan_cached: keyed by device, thread, stream and the contents of the taps) -- ~45 us per call instead of ~1 ms.  The handle is
