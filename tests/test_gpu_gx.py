@@ -2,8 +2,9 @@
 7-smooth transform sizes WITHOUT a compile-time schedule -- what nextfastfft (util.jl:134) returns for most frame lengths, and every default call
 (n = length(s) >> 3, periodograms.jl:560, :647, :828, :872) on a 65 537 .. 400 000-sample signal.  Sizes cover: one workgroup per transform (R0 = 1; one
 and two LDS buffers, 256 and 512 threads, every radix 2 .. 16 in first / middle / last position), the fused column step (nfft = R0 x S: 8400, 12500,
-16384, 20000, 40000 -- VERDICT r5 item 1 -- and an odd size; in Float32 on the compile-time row kernels of csrc/spectral_ctcols.hip where R0 x S is one of
-theirs), zero padding, odd frame counts, several channels.
+16384, 20000, 40000 -- VERDICT r5 item 1 -- and an odd size; in Float32 on the compile-time rows of 8193 .. 16384 points of csrc/spectral_ctcols_big.hip where
+R0 x S is one of theirs -- no Float32 size takes the rows of csrc/spectral_ctcols.hip at the default tunables any more, only Float64 ones do), zero padding, odd
+frame counts, several channels.
 
     Float32 / ComplexF32:  norm-wise <= 5e-6 and element-wise |err| <= 8 log2(nfft) ulp of the largest bin
     Float64 / ComplexF64:  norm-wise <= 1e-12
