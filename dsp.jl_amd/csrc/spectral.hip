@@ -33,6 +33,7 @@
 #include "fft_wg.h"
 #include "hostfft.h"
 #include "rocfft_wrap.h"
+#include "spectral_tables.h"
 #include "welch_plan.h"
 #include "hostpipe.h"
 #include "gx_kernels.h"   // (namespace mdsp::gx and the kernel template: ahead of the anonymous namespace that includes spectral_gx.h)
@@ -765,35 +766,8 @@ int choose_spectral_route(int engine, int dtype, int64_t nfft, int kind, SpecRou
     return MDSP_OK;
 }
 
-// the window as the lean compile-time schedules read it (spectral_gen.h ct_pass0_lean): nfft values in the working precision, ones without a window, zero tail
-template <typename R> __global__ __launch_bounds__(256) void lean_window_kernel(const double* __restrict__ win, R* __restrict__ out, int n, int nfft) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i < nfft) out[i] = i < n ? (win ? (R)win[i] : (R)1) : (R)0;
-}
-template <typename R> int lean_window(DevBuf& buf, const double* win, int n, int64_t nfft, hipStream_t st) {
-    MDSP_TRY(buf.reserve(sizeof(R) * (size_t)nfft));
-    hipLaunchKernelGGL(lean_window_kernel<R>, dim3((unsigned)cdiv(nfft, 256)), dim3(256), 0, st, win, buf.as<R>(), n, (int)nfft);
-    MDSP_LAUNCH_CHECK();
-    return MDSP_OK;
-}
+// the lean compile-time schedules (spectral_gen.h ct_pass0_lean) read the window in the working precision: nfft values, ones without a window, zero tail
 constexpr bool lean_window_needed(int64_t nfft, bool dbl) { return dbl && MDSP_F64_LEAN && nfft >= 4800; }   // (wherever gen_ct_f64_tw2l may set flag 4096)
-
-template <typename R> int upload_roots(DevBuf& buf, int64_t n) {
-    std::vector<cx<R>> w((size_t)n);
-    for (int64_t k = 0; k < n; ++k) {
-        const zd r = unit_root(k, n, -1);
-        w[(size_t)k] = {(R)r.real(), (R)r.imag()};
-    }
-    MDSP_TRY(buf.reserve(sizeof(cx<R>) * (size_t)n));
-    MDSP_HIP(hipMemcpy(buf.p, w.data(), sizeof(cx<R>) * (size_t)n, hipMemcpyHostToDevice));
-    return MDSP_OK;
-}
-
-// the plan's table of nfft roots, for the routes whose kernels read it (the others build their own, much shorter, tables)
-int upload_plan_roots(DevBuf& table, int route, int dtype, int64_t nfft) {
-    if (route != MDSP_ROUTE_POW2 && route != MDSP_ROUTE_GEN) return MDSP_OK;
-    return dtype_is_double(dtype) ? upload_roots<double>(table, nfft) : upload_roots<float>(table, nfft);
-}
 
 int check_split(int64_t n, int64_t noverlap, int64_t nfft) {
     if (n < 1) MDSP_FAIL(MDSP_ERR_DOMAIN, "n (%lld) must be positive", (long long)n);
@@ -1483,8 +1457,7 @@ int welch_accumulate_fused(mdsp_welch_plan_s* pl, const void* s, int64_t len, in
             g.len = len; g.lds_ = lds_; g.K = K; g.hop = hop; g.nch = nch; g.units_per_ch = CPLX ? K : cdiv(K, 2);
             g.n = (int)pl->n; g.N = (int)N; g.nout = (int)pl->nout; g.onesided = pl->onesided; g.r = pl->r;
             if (lean_window_needed(N, sizeof(R) == 8)) {
-                if (!pl->winr_ready) MDSP_TRY(lean_window<R>(pl->winr, win, g.n, N, st));
-                pl->winr_ready = true;
+                if (!pl->winr.p) MDSP_FAIL(MDSP_ERR_ASSERTION, "the working-precision window of nfft=%lld was not built at plan creation", (long long)N);
                 g.winr = pl->winr.p;
             }
             MDSP_TRY((gen_launch<R, CPLX, 0>(g, nch, st, &ngroups, &pl->partial)));
@@ -1501,16 +1474,16 @@ int welch_accumulate_fused(mdsp_welch_plan_s* pl, const void* s, int64_t len, in
             MDSP_TRY(ctbig_welch(pl->ctcols, pl->dtype, s, lds_, K, hop, nch, (int)pl->n, N, win, st, &ngroups, &pl->partial));
             break;
         case MDSP_ROUTE_CTCOLS_BIG:   // R0 x a row size with a compile-time schedule (spectral_ctcols*.hip)
-            MDSP_TRY(ctcols_big_welch(pl->ctcols, pl->dtype, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, win, st, &ngroups, &pl->partial));
+            MDSP_TRY(ctcols_big_welch(pl->ctcols, pl->dtype, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, st, &ngroups, &pl->partial));
             break;
         case MDSP_ROUTE_CTCOLS_F64:
-            MDSP_TRY(ctcols64_welch(pl->ctcols, CPLX, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, win, st, &ngroups, &pl->partial));
+            MDSP_TRY(ctcols64_welch(pl->ctcols, CPLX, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, st, &ngroups, &pl->partial));
             break;
         case MDSP_ROUTE_CTCOLS:
-            MDSP_TRY(ctcols_welch(pl->ctcols, pl->dtype, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, win, st, &ngroups, &pl->partial));
+            MDSP_TRY(ctcols_welch(pl->ctcols, pl->dtype, s, lds_, K, hop, nch, (int)pl->n, N, pl->r0, st, &ngroups, &pl->partial));
             break;
         case MDSP_ROUTE_CTROWS:   // nfft = R0 x S in two kernels (spectral_ctrows.hip): straight into the accumulator
-            MDSP_TRY(ctrows_welch(pl->ctrows, pl->dtype, pl->r0, s, lds_, K, hop, nch, (int)pl->n, N, win, pl->reduced.as<double>(), pl->acc_fresh, st));
+            MDSP_TRY(ctrows_welch(pl->ctrows, pl->dtype, pl->r0, s, lds_, K, hop, nch, (int)pl->n, N, pl->reduced.as<double>(), pl->acc_fresh, st));
             set_fused_sums(pl);
             return MDSP_OK;
         case MDSP_ROUTE_BIG: {   // nfft above the one-workgroup sizes: channel by channel through the multi-pass engine, straight into the accumulator
@@ -1525,6 +1498,42 @@ int welch_accumulate_fused(mdsp_welch_plan_s* pl, const void* s, int64_t len, in
     MDSP_TRY(reduce_partials(pl, pl->partial.as<double>(), pl->reduced.as<double>(), (int)ngroups, nch, (int)N, pl->acc_fresh ? 0 : 1, st));
     set_fused_sums(pl);
     return MDSP_OK;
+}
+
+// Every table the plan's route reads, built once at plan creation from host data (synchronous copies: complete before the plan exists, whatever stream the
+// first exec runs on).  The exec functions above upload nothing; one that finds a table missing fails.
+int prepare_welch_tables(mdsp_welch_plan_s* pl, const double* window_host) {
+    const bool dbl = dtype_is_double(pl->dtype);
+    const int n = (int)pl->n;
+    const int64_t N = pl->nfft, S = pl->r0 > 0 ? N / pl->r0 : N;
+    switch (pl->route) {
+        case MDSP_ROUTE_POW2:
+            MDSP_TRY(upload_roots(pl->table, dbl, N));
+            if (N == w64::N && pl->dtype == MDSP_F32) MDSP_TRY(w64::w64asm_prepare(pl->w64prep, window_host, n));
+            return MDSP_OK;
+        case MDSP_ROUTE_GEN:
+            MDSP_TRY(upload_roots(pl->table, dbl, N));
+            if (lean_window_needed(N, dbl)) MDSP_TRY(upload_window(pl->winr, dbl, window_host, n, N));
+            return MDSP_OK;
+        case MDSP_ROUTE_GX:
+            MDSP_TRY(dbl ? gx_prepare<double>(pl->gx, pl->dtype, N, true) : gx_prepare<float>(pl->gx, pl->dtype, N, true));
+            return upload_window(pl->gx.win, dbl, window_host, n, N);
+        case MDSP_ROUTE_CTBIG:
+            MDSP_TRY(upload_roots(pl->ctcols.roots, dbl, N));
+            return upload_window(pl->ctcols.win, dbl, window_host, n, N);
+        case MDSP_ROUTE_CTCOLS:
+        case MDSP_ROUTE_CTCOLS_BIG:
+        case MDSP_ROUTE_CTCOLS_F64:
+            MDSP_TRY(upload_roots(pl->ctcols.roots, dbl, S));
+            MDSP_TRY(upload_roots(pl->ctcols.rootsN, dbl, N));
+            return upload_window(pl->ctcols.win, dbl, window_host, n, N);
+        case MDSP_ROUTE_CTROWS:   // the column kernel's tables, and the row kernel's: S-point transforms of whole rows, no window
+            MDSP_TRY(upload_roots(pl->ctrows.rootsN, dbl, N));
+            MDSP_TRY(upload_window(pl->ctrows.win, dbl, window_host, n, N));
+            MDSP_TRY(upload_roots(pl->ctrows.rows.roots, dbl, S));
+            return upload_window(pl->ctrows.rows.win, dbl, nullptr, (int)S, S);
+        default: return MDSP_OK;   // the multi-pass engine builds its own at first use (bigfft.hip); rocFFT has none
+    }
 }
 
 }  // namespace
@@ -1608,7 +1617,7 @@ int mdsp_welch_plan_create(mdsp_welch_plan* plan, int64_t n, int64_t noverlap, i
         if (st == MDSP_OK && hipMemcpy(pl->win.p, window_host, sizeof(double) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
             st = set_error(MDSP_ERR_DEVICE, "window upload failed");
     }
-    if (st == MDSP_OK) st = upload_plan_roots(pl->table, pl->route, dtype, nfft);
+    if (st == MDSP_OK) st = prepare_welch_tables(pl, window_host);
     if (st != MDSP_OK) {
         delete pl;
         return st;
@@ -1894,7 +1903,7 @@ int stft_exec_fused(mdsp_stft_plan_s* pl, const void* s, int64_t len, int64_t nc
             g.units_per_ch = CPLX ? K : cdiv(K, 2);
             g.n = (int)pl->n; g.N = (int)pl->nfft; g.nout = (int)pl->nout; g.onesided = pl->onesided; g.psd = pl->psd_only; g.accumulate = pl->accumulate; g.r = pl->r;
             if (CPLX && lean_window_needed(pl->nfft, sizeof(R) == 8)) {   // (per launch: the window pointer of a multitaper plan changes between tapers)
-                MDSP_TRY(lean_window<R>(pl->winr, win, g.n, pl->nfft, st));
+                MDSP_TRY(convert_window(pl->winr, true, win, g.n, pl->nfft, st));
                 g.winr = pl->winr.p;
             }
             int64_t nslots = 0;
@@ -1939,6 +1948,19 @@ int stft_dispatch(mdsp_stft_plan_s* plan, const void* s_dev, int64_t len, int64_
                : stft_exec_fused<float, false>(plan, s_dev, len, nch, lds_, out_dev, ldo, chs, st);
 }
 
+// The root tables of the plan's route, at plan creation (multitaper plans: of their STFT plan).  The working-precision window of the column kernels stays
+// per launch: a multitaper plan points win_ptr at another taper for each pass (convert_window at those sites).
+int prepare_stft_tables(mdsp_stft_plan_s* pl) {
+    const bool dbl = dtype_is_double(pl->dtype);
+    switch (pl->route) {
+        case MDSP_ROUTE_POW2:
+        case MDSP_ROUTE_GEN: return upload_roots(pl->table, dbl, pl->nfft);
+        case MDSP_ROUTE_GX: return dbl ? gx_prepare<double>(pl->gx, pl->dtype, pl->nfft, false) : gx_prepare<float>(pl->gx, pl->dtype, pl->nfft, false);
+        case MDSP_ROUTE_CTBIG_COLS: return upload_roots(pl->ctbig.roots, dbl, pl->nfft);
+        default: return MDSP_OK;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1973,7 +1995,7 @@ int mdsp_stft_plan_create(mdsp_stft_plan* plan, int64_t n, int64_t noverlap, int
             st = set_error(MDSP_ERR_DEVICE, "window upload failed");
         pl->win_ptr = pl->win.as<double>();
     }
-    if (st == MDSP_OK) st = upload_plan_roots(pl->table, pl->route, dtype, nfft);
+    if (st == MDSP_OK) st = prepare_stft_tables(pl);
     if (st != MDSP_OK) {
         delete pl;
         return st;
@@ -2168,7 +2190,7 @@ int mdsp_mt_plan_create(mdsp_mt_plan* plan, int64_t n, int64_t nfft, const doubl
     for (int64_t k = 0; k < ntapers; ++k) w[(size_t)k] = 1.0 / r_host[k];
     MDSP_TRY(pl->rinv.reserve(sizeof(double) * (size_t)ntapers));
     MDSP_HIP(hipMemcpy(pl->rinv.p, w.data(), sizeof(double) * (size_t)ntapers, hipMemcpyHostToDevice));
-    MDSP_TRY(upload_plan_roots(st.table, st.route, dtype, nfft));
+    MDSP_TRY(prepare_stft_tables(&st));
     *plan = pl.release();
     return MDSP_OK;
 }

@@ -33,23 +33,6 @@ template <typename R, bool CPLX> int big_dispatch(GenArgs& a, int64_t nch, hipSt
     }
 }
 
-// the window in the working precision for the lean schedules (ct_pass0_lean): ones without a window, zeros behind n
-__global__ __launch_bounds__(256) void big_window_kernel(const double* __restrict__ win, float* __restrict__ out, int n, int nfft) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i < nfft) out[i] = i < n ? (win ? (float)win[i] : 1.0f) : 0.0f;
-}
-
-template <typename R> int upload_roots_n(DevBuf& buf, int64_t n) {
-    std::vector<cx<R>> w((size_t)n);
-    for (int64_t k = 0; k < n; ++k) {
-        const zd r = unit_root(k, n, -1);
-        w[(size_t)k] = {(R)r.real(), (R)r.imag()};
-    }
-    MDSP_TRY(buf.reserve(sizeof(cx<R>) * (size_t)n));
-    MDSP_HIP(hipMemcpy(buf.p, w.data(), sizeof(cx<R>) * (size_t)n, hipMemcpyHostToDevice));
-    return MDSP_OK;
-}
-
 }  // namespace
 
 namespace mdsp {
@@ -82,13 +65,7 @@ int ctbig_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t 
                 hipStream_t st, int64_t* nslots, DevBuf* partial, int accumulate) {
     if (!ctbig_ok(dtype, nfft)) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld has no single-workgroup compile-time schedule", (long long)nfft);
     if (dtype_is_double(dtype)) return ctbig64_welch(cp, dtype_is_complex(dtype), s, lds_, K, hop, nch, n, nfft, win_dev, st, nslots, partial, accumulate);
-    if (!cp.ready) {
-        MDSP_TRY(upload_roots_n<float>(cp.roots, nfft));
-        MDSP_TRY(cp.win.reserve(sizeof(float) * (size_t)nfft));
-        hipLaunchKernelGGL(big_window_kernel, dim3((unsigned)cdiv(nfft, 256)), dim3(256), 0, st, win_dev, cp.win.as<float>(), n, (int)nfft);
-        MDSP_LAUNCH_CHECK();
-        cp.ready = true;
-    }
+    if (!cp.roots.p || !cp.win.p) MDSP_FAIL(MDSP_ERR_ASSERTION, "the tables of nfft=%lld were not built at plan creation", (long long)nfft);
     const bool cplx = dtype_is_complex(dtype);
     GenArgs g{};
     g.s = s; g.roots = cp.roots.p; g.win = win_dev; g.winr = cp.win.p;

@@ -11,6 +11,7 @@
 #include "fft_lds.h"
 #include "hostfft.h"
 #include "spectral_ctcols.h"
+#include "spectral_tables.h"
 
 using namespace mdsp;
 using mdsp::fft::cx;
@@ -39,11 +40,6 @@ template <typename R, bool CPLX> int cols_dispatch(GenArgs& a, int64_t nch, hipS
     }
     MDSP_FAIL(MDSP_ERR_ASSERTION, "no single-workgroup column schedule of %d points", a.N);
 }
-
-__global__ __launch_bounds__(256) void cols_window_kernel(const double* __restrict__ win, float* __restrict__ out, int n, int nfft) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i < nfft) out[i] = i < n ? (win ? (float)win[i] : 1.0f) : 0.0f;
-}
 }  // namespace
 
 namespace mdsp {
@@ -64,22 +60,10 @@ bool ctbig_cols_ok(int dtype, int64_t nfft) {
 int ctbig_stft(CtColsPlan& cp, int dtype, const CtBigColsArgs& c, hipStream_t st) {
     if (!ctbig_cols_ok(dtype, c.nfft)) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld has no single-workgroup column schedule", (long long)c.nfft);
     if (dtype_is_double(dtype)) return ctbig64_stft(cp, dtype_is_complex(dtype), c, st);
-    if (!cp.ready) {
-        std::vector<cx<float>> w((size_t)c.nfft);
-        for (int64_t k = 0; k < c.nfft; ++k) {
-            const zd r = unit_root(k, c.nfft, -1);
-            w[(size_t)k] = {(float)r.real(), (float)r.imag()};
-        }
-        MDSP_TRY(cp.roots.reserve(sizeof(cx<float>) * (size_t)c.nfft));
-        MDSP_HIP(hipMemcpy(cp.roots.p, w.data(), sizeof(cx<float>) * (size_t)c.nfft, hipMemcpyHostToDevice));
-        MDSP_TRY(cp.win.reserve(sizeof(float) * (size_t)c.nfft));
-        cp.ready = true;
-    }
+    if (!cp.roots.p) MDSP_FAIL(MDSP_ERR_ASSERTION, "the roots of nfft=%lld were not built at plan creation", (long long)c.nfft);
     const bool cplx = dtype_is_complex(dtype);
-    if (cplx) {   // (per launch: the window of a multitaper plan changes between tapers; the lean forms load it beside the samples)
-        hipLaunchKernelGGL(cols_window_kernel, dim3((unsigned)cdiv(c.nfft, 256)), dim3(256), 0, st, c.win, cp.win.as<float>(), c.n, (int)c.nfft);
-        MDSP_LAUNCH_CHECK();
-    }
+    // (per launch: the window of a multitaper plan changes between tapers; the lean forms load it beside the samples)
+    if (cplx) MDSP_TRY(convert_window(cp.win, false, c.win, c.n, c.nfft, st));
     GenArgs g{};
     g.s = c.s; g.out = c.out; g.roots = cp.roots.p; g.win = c.win; g.winr = cp.win.p;
     g.len = c.len; g.lds_ = c.lds_; g.K = c.K; g.hop = c.hop; g.nch = c.nch; g.ldo = c.ldo; g.chs = c.chs;

@@ -10,6 +10,7 @@
 #include "fft_lds.h"
 #include "hostfft.h"
 #include "spectral_ctcols.h"
+#include "spectral_tables.h"
 
 using namespace mdsp;
 using mdsp::fft::cx;
@@ -41,24 +42,6 @@ template <bool CPLX, int MODE> int dispatch64(GenArgs& a, int64_t nch, hipStream
     MDSP_FAIL(MDSP_ERR_ASSERTION, "no Float64 single-workgroup compile-time schedule of %d points", a.N);
 }
 
-__global__ __launch_bounds__(256) void window64_kernel(const double* __restrict__ win, double* __restrict__ out, int n, int nfft) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i < nfft) out[i] = i < n ? (win ? win[i] : 1.0) : 0.0;
-}
-
-int prepare64(CtColsPlan& cp, int64_t nfft) {
-    if (cp.ready) return MDSP_OK;
-    std::vector<cx<double>> w((size_t)nfft);
-    for (int64_t k = 0; k < nfft; ++k) {
-        const zd r = unit_root(k, nfft, -1);
-        w[(size_t)k] = {r.real(), r.imag()};
-    }
-    MDSP_TRY(cp.roots.reserve(sizeof(cx<double>) * (size_t)nfft));
-    MDSP_HIP(hipMemcpy(cp.roots.p, w.data(), sizeof(cx<double>) * (size_t)nfft, hipMemcpyHostToDevice));
-    MDSP_TRY(cp.win.reserve(sizeof(double) * (size_t)nfft));
-    cp.ready = true;
-    return MDSP_OK;
-}
 }  // namespace
 
 namespace mdsp {
@@ -77,12 +60,7 @@ bool ctbig64_ok(int64_t nfft) {
 int ctbig64_welch(CtColsPlan& cp, bool cplx, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, const double* win_dev, hipStream_t st,
                   int64_t* nslots, DevBuf* partial, int accumulate) {
     if (!ctbig64_ok(nfft)) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld has no Float64 single-workgroup compile-time schedule", (long long)nfft);
-    const bool fresh = !cp.ready;
-    MDSP_TRY(prepare64(cp, nfft));
-    if (fresh) {   // (a Welch plan's window is fixed)
-        hipLaunchKernelGGL(window64_kernel, dim3((unsigned)cdiv(nfft, 256)), dim3(256), 0, st, win_dev, cp.win.as<double>(), n, (int)nfft);
-        MDSP_LAUNCH_CHECK();
-    }
+    if (!cp.roots.p || !cp.win.p) MDSP_FAIL(MDSP_ERR_ASSERTION, "the tables of nfft=%lld were not built at plan creation", (long long)nfft);
     GenArgs g{};
     g.s = s; g.roots = cp.roots.p; g.win = win_dev; g.winr = cp.win.p;
     g.lds_ = lds_; g.K = K; g.hop = hop; g.nch = nch; g.units_per_ch = cplx ? K : cdiv(K, 2);
@@ -92,11 +70,8 @@ int ctbig64_welch(CtColsPlan& cp, bool cplx, const void* s, int64_t lds_, int64_
 
 int ctbig64_stft(CtColsPlan& cp, bool cplx, const CtBigColsArgs& c, hipStream_t st) {
     if (!ctbig64_ok(c.nfft)) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld has no Float64 single-workgroup column schedule", (long long)c.nfft);
-    MDSP_TRY(prepare64(cp, c.nfft));
-    if (cplx) {   // (per launch: the window of a multitaper plan changes between tapers)
-        hipLaunchKernelGGL(window64_kernel, dim3((unsigned)cdiv(c.nfft, 256)), dim3(256), 0, st, c.win, cp.win.as<double>(), c.n, (int)c.nfft);
-        MDSP_LAUNCH_CHECK();
-    }
+    if (!cp.roots.p) MDSP_FAIL(MDSP_ERR_ASSERTION, "the roots of nfft=%lld were not built at plan creation", (long long)c.nfft);
+    if (cplx) MDSP_TRY(convert_window(cp.win, true, c.win, c.n, c.nfft, st));   // (per launch: the window of a multitaper plan changes between tapers)
     GenArgs g{};
     g.s = c.s; g.out = c.out; g.roots = cp.roots.p; g.win = c.win; g.winr = cp.win.p;
     g.len = c.len; g.lds_ = c.lds_; g.K = c.K; g.hop = c.hop; g.nch = c.nch; g.ldo = c.ldo; g.chs = c.chs;

@@ -4,8 +4,9 @@
 #include "common.h"
 
 namespace mdsp {
-struct CtColsPlan {   // what a Welch plan keeps for it: roots of S and of nfft, the window in working precision
-    bool ready = false;
+// what a plan keeps for these kernels: roots of S and of nfft (one-workgroup forms: `roots` of nfft alone), the window in working precision.  The plan builds
+// them at its creation (spectral_tables.h); an exec that finds one missing fails.
+struct CtColsPlan {
     DevBuf roots, rootsN, win;
 };
 // the column factor R0 in 2 .. 8 with nfft / R0 among the instantiated row sizes (0: none); which of the three row forms below runs is decided with it
@@ -13,15 +14,15 @@ struct CtColsPlan {   // what a Welch plan keeps for it: roots of S and of nfft,
 int ctcols_split(int dtype, int64_t nfft);
 // partial[(group, ch)][nfft] (+ reduce by the caller): Float64 sums of |Z|^2 per bin, natural order -- rows on the mixed-radix compile-time schedules
 int ctcols_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0,
-                 const double* win_dev, hipStream_t st, int64_t* ngroups, DevBuf* partial);
+                 hipStream_t st, int64_t* ngroups, DevBuf* partial);
 // spectral_ctcols_big.hip: rows of 8193 .. 16384 points (the single-workgroup schedules of ctbig_sizes.h)
 bool ctcols_big_row_ok(int dtype, int64_t S);
 int ctcols_big_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0,
-                     const double* win_dev, hipStream_t st, int64_t* ngroups, DevBuf* partial);
+                     hipStream_t st, int64_t* ngroups, DevBuf* partial);
 // spectral_ctcols_f64.hip: Float64 / ComplexF64 rows of 4097 .. 9600 points (the same tables), R0 = 2 .. 8
 bool ctcols64_row_ok(int64_t S);
-int ctcols64_welch(CtColsPlan& cp, bool cplx, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0, const double* win_dev,
-                   hipStream_t st, int64_t* ngroups, DevBuf* partial);
+int ctcols64_welch(CtColsPlan& cp, bool cplx, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0, hipStream_t st,
+                   int64_t* ngroups, DevBuf* partial);
 // spectral_ctbig.hip: nfft between 8193 and 16384 points with a single-workgroup compile-time schedule (Float32 / ComplexF32); cp holds the nfft roots.
 // ctbig_ok / ctbig_cols_ok are the size tables alone (MDSP_GX=3 keeps Float64 off them in spectral.hip choose_spectral_route)
 bool ctbig_ok(int dtype, int64_t nfft);

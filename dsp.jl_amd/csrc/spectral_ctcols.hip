@@ -104,25 +104,12 @@ int ctcols_split(int dtype, int64_t nfft) {
 }
 
 int ctcols_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0,
-                 const double* win_dev, hipStream_t st, int64_t* ngroups, DevBuf* partial) {
+                 hipStream_t st, int64_t* ngroups, DevBuf* partial) {
     if (R0 < 2 || nfft % R0) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld is not %d x a compile-time row size", (long long)nfft, R0);
-    const int64_t S = nfft / R0;
     const bool dbl = dtype_is_double(dtype), cplx = dtype_is_complex(dtype);
-    if (!cp.ready) {
-        MDSP_TRY(dbl ? upload_roots_n<double>(cp.roots, S) : upload_roots_n<float>(cp.roots, S));
-        MDSP_TRY(dbl ? upload_roots_n<double>(cp.rootsN, nfft) : upload_roots_n<float>(cp.rootsN, nfft));
-        MDSP_TRY(cp.win.reserve((dbl ? sizeof(double) : sizeof(float)) * (size_t)nfft));
-        cp.ready = true;
-    }
-    if (dbl) hipLaunchKernelGGL(cols_window_kernel<double>, dim3((unsigned)cdiv(nfft, 256)), dim3(256), 0, st, win_dev, cp.win.as<double>(), n, (int)nfft);
-    else hipLaunchKernelGGL(cols_window_kernel<float>, dim3((unsigned)cdiv(nfft, 256)), dim3(256), 0, st, win_dev, cp.win.as<float>(), n, (int)nfft);
-    MDSP_LAUNCH_CHECK();
-    ColsArgs ca{};
-    ca.g.s = s; ca.g.roots = cp.roots.p; ca.g.lds_ = lds_; ca.g.K = K; ca.g.hop = hop; ca.g.nch = nch;
-    ca.g.units_per_ch = cplx ? K : cdiv(K, 2);
-    ca.g.n = n; ca.g.N = (int)S;
-    ca.winf = cp.win.p; ca.rootsN = cp.rootsN.p; ca.nfft = (int)nfft; ca.R0 = R0;
-    if (dbl) return cplx ? cols_dispatch<double, true>(ca, nch, st, ngroups, partial) : cols_dispatch<double, false>(ca, nch, st, ngroups, partial);
-    return cplx ? cols_dispatch<float, true>(ca, nch, st, ngroups, partial) : cols_dispatch<float, false>(ca, nch, st, ngroups, partial);
+    return cols_welch_run(cp, cplx, s, lds_, K, hop, nch, n, nfft, R0, [&](ColsArgs& ca) {
+        if (dbl) return cplx ? cols_dispatch<double, true>(ca, nch, st, ngroups, partial) : cols_dispatch<double, false>(ca, nch, st, ngroups, partial);
+        return cplx ? cols_dispatch<float, true>(ca, nch, st, ngroups, partial) : cols_dispatch<float, false>(ca, nch, st, ngroups, partial);
+    });
 }
 }  // namespace mdsp

@@ -52,23 +52,11 @@ bool ctcols_big_row_ok(int dtype, int64_t S) {
 }
 
 int ctcols_big_welch(CtColsPlan& cp, int dtype, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0,
-                     const double* win_dev, hipStream_t st, int64_t* ngroups, DevBuf* partial) {
-    const int64_t S = nfft / R0;
-    if (nfft % R0 || !ctcols_big_row_ok(dtype, S)) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld is not %d x a single-workgroup row size", (long long)nfft, R0);
+                     hipStream_t st, int64_t* ngroups, DevBuf* partial) {
+    if (nfft % R0 || !ctcols_big_row_ok(dtype, nfft / R0)) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld is not %d x a single-workgroup row size", (long long)nfft, R0);
     const bool cplx = dtype_is_complex(dtype);
-    if (!cp.ready) {
-        MDSP_TRY(upload_roots_n<float>(cp.roots, S));
-        MDSP_TRY(upload_roots_n<float>(cp.rootsN, nfft));
-        MDSP_TRY(cp.win.reserve(sizeof(float) * (size_t)nfft));
-        cp.ready = true;
-    }
-    hipLaunchKernelGGL(cols_window_kernel<float>, dim3((unsigned)cdiv(nfft, 256)), dim3(256), 0, st, win_dev, cp.win.as<float>(), n, (int)nfft);
-    MDSP_LAUNCH_CHECK();
-    ColsArgs ca{};
-    ca.g.s = s; ca.g.roots = cp.roots.p; ca.g.lds_ = lds_; ca.g.K = K; ca.g.hop = hop; ca.g.nch = nch;
-    ca.g.units_per_ch = cplx ? K : cdiv(K, 2);
-    ca.g.n = n; ca.g.N = (int)S;
-    ca.winf = cp.win.p; ca.rootsN = cp.rootsN.p; ca.nfft = (int)nfft; ca.R0 = R0;
-    return cplx ? big_rows_dispatch<float, true>(ca, nch, st, ngroups, partial) : big_rows_dispatch<float, false>(ca, nch, st, ngroups, partial);
+    return cols_welch_run(cp, cplx, s, lds_, K, hop, nch, n, nfft, R0, [&](ColsArgs& ca) {
+        return cplx ? big_rows_dispatch<float, true>(ca, nch, st, ngroups, partial) : big_rows_dispatch<float, false>(ca, nch, st, ngroups, partial);
+    });
 }
 }  // namespace mdsp

@@ -176,11 +176,6 @@ __global__ __launch_bounds__(S::T, (sizeof(cx<R>) * S::NP > 80 * 1024 && S::T > 
     flush();
 }
 
-template <typename R> __global__ __launch_bounds__(256) void cols_window_kernel(const double* __restrict__ win, R* __restrict__ out, int n, int nfft) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < nfft) out[i] = i < n ? (win ? (R)win[i] : (R)1) : (R)0;
-}
-
 template <typename R, bool CPLX, typename S> int cols_launch(ColsArgs& ca, int64_t nch, hipStream_t st, int64_t* ngroups, DevBuf* partial) {
     auto kern = gen_ct_cols_kernel<R, CPLX, S>;
     GenArgs& a = ca.g;
@@ -203,14 +198,15 @@ template <typename R, bool CPLX, typename S> int cols_launch(ColsArgs& ca, int64
     return MDSP_OK;
 }
 
-template <typename R> int upload_roots_n(DevBuf& buf, int64_t n) {
-    std::vector<cx<R>> w((size_t)n);
-    for (int64_t k = 0; k < n; ++k) {
-        const zd r = unit_root(k, n, -1);
-        w[(size_t)k] = {(R)r.real(), (R)r.imag()};
-    }
-    MDSP_TRY(buf.reserve(sizeof(cx<R>) * (size_t)n));
-    MDSP_HIP(hipMemcpy(buf.p, w.data(), sizeof(cx<R>) * (size_t)n, hipMemcpyHostToDevice));
-    return MDSP_OK;
+// What ctcols_welch, ctcols_big_welch and ctcols64_welch share: the plan's tables (built at plan creation) into ColsArgs, then `dispatch(ca)` -- the
+// switch over the row sizes their translation unit instantiates.
+template <typename Dispatch>
+int cols_welch_run(const CtColsPlan& cp, bool cplx, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, int R0, Dispatch&& dispatch) {
+    if (!cp.roots.p || !cp.rootsN.p || !cp.win.p) MDSP_FAIL(MDSP_ERR_ASSERTION, "the row tables of nfft=%lld were not built at plan creation", (long long)nfft);
+    ColsArgs ca{};
+    ca.g.s = s; ca.g.roots = cp.roots.p; ca.g.lds_ = lds_; ca.g.K = K; ca.g.hop = hop; ca.g.nch = nch;
+    ca.g.units_per_ch = cplx ? K : cdiv(K, 2);
+    ca.g.n = n; ca.g.N = (int)(nfft / R0);
+    ca.winf = cp.win.p; ca.rootsN = cp.rootsN.p; ca.nfft = (int)nfft; ca.R0 = R0;
+    return dispatch(ca);
 }
-

@@ -110,11 +110,6 @@ __global__ __launch_bounds__(256) void rows_reduce_kernel(const double* __restri
     }
 }
 
-template <typename R> __global__ __launch_bounds__(256) void rows_window_kernel(const double* __restrict__ win, R* __restrict__ out, int n, int nfft) {
-    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i < nfft) out[i] = i < n ? (win ? (R)win[i] : (R)1) : (R)0;
-}
-
 template <bool CPLX, typename R> int launch_cols(int R0, const RowsColArgs& a, int64_t nch, hipStream_t st) {
     const dim3 grid((unsigned)cdiv(a.S, 256), (unsigned)a.cnt, (unsigned)nch);
     switch (R0) {
@@ -153,24 +148,12 @@ int ctrows_split(int dtype, int64_t nfft, int r0_min) {
 }
 
 template <typename R>
-static int ctrows_run(CtRowsPlan& rp, bool cplx, int R0, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, const double* win_dev, double* acc,
-                      bool fresh, hipStream_t st) {
+static int ctrows_run(CtRowsPlan& rp, bool cplx, int R0, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, double* acc, bool fresh,
+                      hipStream_t st) {
     const int64_t S = nfft / R0;
     const int64_t units = cplx ? K : cdiv(K, 2);
     if (units == 0) return MDSP_OK;
-    if (!rp.ready) {
-        std::vector<cx<R>> w((size_t)nfft);
-        for (int64_t k = 0; k < nfft; ++k) {
-            const zd r = unit_root(k, nfft, -1);
-            w[(size_t)k] = {(R)r.real(), (R)r.imag()};
-        }
-        MDSP_TRY(rp.rootsN.reserve(sizeof(cx<R>) * (size_t)nfft));
-        MDSP_HIP(hipMemcpy(rp.rootsN.p, w.data(), sizeof(cx<R>) * (size_t)nfft, hipMemcpyHostToDevice));
-        MDSP_TRY(rp.win.reserve(sizeof(R) * (size_t)nfft));
-        hipLaunchKernelGGL(rows_window_kernel<R>, dim3((unsigned)cdiv(nfft, 256)), dim3(256), 0, st, win_dev, rp.win.as<R>(), n, (int)nfft);
-        MDSP_LAUNCH_CHECK();
-        rp.ready = true;
-    }
+    if (!rp.rootsN.p || !rp.win.p) MDSP_FAIL(MDSP_ERR_ASSERTION, "the column tables of nfft=%lld were not built at plan creation", (long long)nfft);
     const int rowtype = sizeof(R) == 8 ? MDSP_C64 : MDSP_C32;
     const int64_t per = (int64_t)sizeof(cx<R>) * nfft * nch;   // work bytes per unit
     const int mib = std::max(16, tunables().big_chunk_mib);
@@ -195,11 +178,10 @@ static int ctrows_run(CtRowsPlan& rp, bool cplx, int R0, const void* s, int64_t 
     return MDSP_OK;
 }
 
-int ctrows_welch(CtRowsPlan& rp, int dtype, int R0, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, const double* win_dev,
-                 double* acc, bool fresh, hipStream_t st) {
+int ctrows_welch(CtRowsPlan& rp, int dtype, int R0, const void* s, int64_t lds_, int64_t K, int64_t hop, int64_t nch, int n, int64_t nfft, double* acc, bool fresh,
+                 hipStream_t st) {
     const bool dbl = dtype_is_double(dtype), cplx = dtype_is_complex(dtype);
     if (nfft % R0 || !radix_ok(R0) || !row_ok(dbl, nfft / R0)) MDSP_FAIL(MDSP_ERR_ASSERTION, "nfft=%lld is not %d rows of a single-workgroup size", (long long)nfft, R0);
-    return dbl ? ctrows_run<double>(rp, cplx, R0, s, lds_, K, hop, nch, n, nfft, win_dev, acc, fresh, st)
-               : ctrows_run<float>(rp, cplx, R0, s, lds_, K, hop, nch, n, nfft, win_dev, acc, fresh, st);
+    return dbl ? ctrows_run<double>(rp, cplx, R0, s, lds_, K, hop, nch, n, nfft, acc, fresh, st) : ctrows_run<float>(rp, cplx, R0, s, lds_, K, hop, nch, n, nfft, acc, fresh, st);
 }
 }  // namespace mdsp

@@ -5,11 +5,6 @@
 #include "gx_kernels.h"
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-template <typename R> __global__ __launch_bounds__(256) void gx_window_kernel(const double* __restrict__ win, R* __restrict__ out, int n, int nfft) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < nfft) out[i] = i < n ? (win ? (R)win[i] : (R)1) : (R)0;
-}
-
 constexpr int GX_LDS_BYTES = 160 * 1024;
 constexpr int GX_R0_MAX = 8;    // column factor at most (R0 loads per point, R0 - 1 of them from the L2: 125000 = 20 x 6250 measured 3.0 ms against the multi-pass engine's 1.2)
 constexpr int GX_R0_LAST = 32;  // ... and for the few sizes below 50000 points that no R0 <= 8 splits (19683 = 9 x 2187, 46875 = 15 x 3125): still ahead of the rocFFT pipeline
@@ -67,8 +62,8 @@ inline int gx_split_r0(int dtype, int64_t nfft) {
 }
 inline bool gx_size_ok(int dtype, int64_t nfft) { return gx_split_r0(dtype, nfft) > 0; }
 
+// at plan creation: the schedule, the split and the twiddle tables
 template <typename R> int gx_prepare(GxPlan& gp, int dtype, int64_t nfft, bool welch) {
-    if (gp.ready) return MDSP_OK;
     if (!gx_choose(dtype, nfft, welch, &gp.R0, &gp.sc)) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "nfft=%lld has no single-workgroup schedule", (long long)nfft);
     const int64_t S = gp.sc.N;
     gp.nhs = mdsp::gx::tw_hi_entries(S);
@@ -103,18 +98,16 @@ template <typename R> int gx_prepare(GxPlan& gp, int dtype, int64_t nfft, bool w
     }
     MDSP_TRY(gp.tw.reserve(sizeof(cx<R>) * tab.size()));
     MDSP_HIP(hipMemcpy(gp.tw.p, tab.data(), sizeof(cx<R>) * tab.size(), hipMemcpyHostToDevice));
-    MDSP_TRY(gp.win.reserve(sizeof(R) * (size_t)nfft));
     gp.lds_bytes = sizeof(cx<R>) * ((size_t)gp.sc.np * (size_t)gp.sc.nbuf + (size_t)ntab) + (welch ? sizeof(R) * (size_t)S : 0);
-    gp.ready = true;
     return MDSP_OK;
 }
 
-// a.s, lds_, K, hop, nch, n, nfft, nout, onesided, psd, accumulate, r, ldo, chs, out (columns) filled by the caller
+// a.s, lds_, K, hop, nch, n, nfft, nout, onesided, psd, accumulate, r, ldo, chs, out (columns) filled by the caller.  Welch sums (MODE 0) read the window the
+// plan built at its creation; columns convert the window of THIS launch (win_dev: a multitaper plan's changes between tapers)
 template <typename R, bool CPLX, int MODE>
 int gx_launch(GxPlan& gp, GxArgs& a, const double* win_dev, int dtype, hipStream_t st, int64_t* ngroups_out, DevBuf* partial) {
-    MDSP_TRY(gx_prepare<R>(gp, dtype, a.nfft, MODE == 0));
-    hipLaunchKernelGGL(gx_window_kernel<R>, dim3((unsigned)cdiv(a.nfft, 256)), dim3(256), 0, st, win_dev, gp.win.as<R>(), a.n, a.nfft);
-    MDSP_LAUNCH_CHECK();
+    if (!gp.tw.p || (MODE == 0 && !gp.win.p)) MDSP_FAIL(MDSP_ERR_ASSERTION, "the run-time schedule of nfft=%d was not prepared at plan creation", a.nfft);
+    if (MODE != 0) MDSP_TRY(convert_window(gp.win, sizeof(R) == 8, win_dev, a.n, a.nfft, st));
     a.sc = gp.sc;
     a.nbuf = gp.sc.nbuf;
     a.R0 = gp.R0;

@@ -31,11 +31,11 @@ struct mdsp_welch_plan_s {
     mdsp::DevBuf redtmp;         // group sums of the two-step slice reduction (reduce_partials, spectral.hip)
     mdsp::big::EngineHolder big;   // nfft above the single-workgroup kernels: the multi-pass engine (bigfft.hip), built at the first accumulate
     mdsp::GxPlan gx;             // 7-smooth sizes without a compile-time schedule, up to 32 x 16384 points: the run-time-schedule kernel (spectral_gx.h)
+    // (the tables of the plan's route -- table, winr, gx, ctrows, ctcols, w64prep -- are built at its creation: spectral.hip prepare_welch_tables)
     mdsp::DevBuf winr;           // lean compile-time schedules (CtSched flag 4096): the window in the working precision, nfft values, zero tail
-    bool winr_ready = false;
     mdsp::CtRowsPlan ctrows;     // ... or R0 x S in two kernels from R0 = 5 (spectral_ctrows.hip)
     mdsp::CtColsPlan ctcols;     // ... and those that are R0 x a compile-time row schedule (spectral_ctcols.hip)
-    mdsp::DevBuf w64prep;        // mdsp_welch_w64_asm: Float32 window pairs + per-lane twiddles (built at the plan's first launch of that kernel)
+    mdsp::DevBuf w64prep;        // mdsp_welch_w64_asm: Float32 window pairs + per-lane twiddles (nfft 4096, real Float32)
     bool frames_on_device = false;
     bool sums_global = false;    // the sums are totals over ranks (mdsp_welch_allreduce ran): only mdsp_welch_reset clears it -- accumulating into them
                                  // and reducing again would add the earlier global totals nranks times
