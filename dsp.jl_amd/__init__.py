@@ -27,6 +27,7 @@ from .multitaper import (MTConfig, MTSpectrogramConfig, MTCrossSpectraConfig, MT
 from .periodograms import (Periodogram, Periodogram2, Spectrogram, WelchConfig, arraysplit, fftshift, periodogram, welch_pgram, welch_pgram_,  # noqa: F401
                            spectrogram, stft, power, freq, time, frame_count)
 from .unwrap import unwrap, unwrap_, unwrap_geometry, UnwrapPlan  # noqa: F401
+from .response import freqresp, phaseresp, grpdelay, impresp, stepresp, RespPlan, resp_geometry  # noqa: F401
 from .comm import Comm  # noqa: F401
 from .channels import (channel_shard, welch_channel_mean, frame_shard, frame_span, welch_time_split,  # noqa: F401
                        filt_time_split_span, filt_time_split)

@@ -21,6 +21,10 @@ OLS_FILT, OLS_CONV = 0, 1
 UNWRAP_CONTIGUOUS, UNWRAP_STRIDED = 0, 1
 REDUCE_SUMABS2, REDUCE_SUMABS2_W, REDUCE_ABSARGMAX = 0, 1, 2
 REDUCE_CONTIGUOUS, REDUCE_STRIDED = 0, 1
+RESP_POLY, RESP_SECTIONS, RESP_ZPK = 0, 1, 2
+RESP_DERIV, RESP_NEG = 1, 2
+RESP_COMPLEX, RESP_ANGLE, RESP_REAL_MINUS = 0, 1, 2
+RESP_W, RESP_POINTS = 0, 1
 SHIFT_AUTO, SHIFT_DISJOINT, SHIFT_HALO, SHIFT_STAGED = 0, 1, 2, 3
 HOST_PINNED = 1
 COMM_ID_BYTES = 128
@@ -134,6 +138,12 @@ PROTOTYPES = {
     "mdsp_sos_exec": (ci, [vp, vp, i64, vp, i64, vp, ci, vp]),
     "mdsp_sos_geometry_for": (ci, [i64, ci, i64, i64, i64, pi64, pi64, pi64, pi64, pi64]),
     "mdsp_sos_emulate_host": (ci, [vp, i64, vp, i64, vp, pdbl, i64, cd, ci, ci, i64, i64, i64, ci]),
+    "mdsp_resp_plan_create": (ci, [pvp, ci, ci, ci, ci, ci, pdbl, i64, pdbl, i64, cd, cd, i64, i64]),
+    "mdsp_resp_plan_destroy": (ci, [vp]),
+    "mdsp_resp_plan_info": (ci, [vp, pi64, pi64, pi64]),
+    "mdsp_resp_exec": (ci, [vp, vp, vp, vp]),
+    "mdsp_resp_geometry_for": (ci, [ci, ci, i64, ci, i64, i64, pi64, pi64, pi64]),
+    "mdsp_resp_emulate_host": (ci, [vp, vp, ci, ci, ci, ci, pdbl, i64, pdbl, i64, cd, cd, i64, i64]),
     "mdsp_reduce_plan_create": (ci, [pvp, i64, i64, i64, ci, ci, cd, i64, i64]),
     "mdsp_reduce_plan_destroy": (ci, [vp]),
     "mdsp_reduce_plan_info": (ci, [vp, pint, pi64, pi64, pi64, pi64]),

@@ -168,7 +168,7 @@ def _pr_from(f) -> PolynomialRatio:
     if isinstance(f, ZeroPoleGain):                                    # :160-164: b = real(k fromroots(z)), a = real(fromroots(p)), shifted to z^-1
         dt = util.promote_type(f.dtype, f.kdtype)
         dt = dt if dt in (_F32, _F64) else _F64
-        b, a = np.real(f.k * np.poly(f.z)), np.real(np.poly(f.p))
+        b, a = np.atleast_1d(np.real(f.k * np.poly(f.z))), np.atleast_1d(np.real(np.poly(f.p)))   # (np.poly of no roots is the scalar 1)
         n = max(len(b), len(a))
         b, a = np.concatenate([np.zeros(n - len(b)), b]), np.concatenate([np.zeros(n - len(a)), a])
         lead = next((i for i in range(n) if a[i] != 0 or b[i] != 0), 0)   # the highest power present becomes z^0

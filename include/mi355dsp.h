@@ -393,6 +393,48 @@ int mdsp_sos_emulate_host(const void* x_host, int64_t ldx, void* y_host, int64_t
                           double gain, int has_gain, int dtype, int64_t n, int64_t ncols, int64_t segments, int reverse);
 
 /* ------------------------------------------------------------------------------------------------------
+ * freqresp / phaseresp / grpdelay (Filters/response.jl:27-52, :73-76, :96-111) of a :z-domain filter with real coefficients: a rational function
+ * evaluated at nw points of the unit circle, a lane per point (csrc/resp_op.h).
+ *   dtype: MDSP_F32 or MDSP_F64, the REAL type of the working type (ComplexF32 / ComplexF64).  Every coefficient is rounded to it first.
+ *   form MDSP_RESP_POLY:      num(y) / den(y), num = sum num[k] y^k (nnum >= 1), den = sum den[k] y^k, or 1 when nden == 0; Horner from the highest
+ *                             coefficient.  MDSP_RESP_DERIV: coefficient k of the numerator is k * num[k], the product rounded once (response.jl:106);
+ *                             den == num with nden == nnum is one device array (what grpdelay passes).  gain is not used.
+ *        MDSP_RESP_SECTIONS:  gain * prod_k biquad_k(x), left to right from one; num: nnum x 5 doubles b0 b1 b2 a1 a2 (0 <= nnum <= 16), nden == 0;
+ *                             biquad(x) = fma(fma(b0, x, b1), x, b2) / fma(x + a1, x, a2) (response.jl:49-52).
+ *        MDSP_RESP_ZPK:       (gain * prod (x - z_i)) / prod (x - p_i) (response.jl:47-48); num: nnum zeros, den: nden poles, (re, im) pairs of doubles.
+ *   out_mode MDSP_RESP_COMPLEX: H, nw complex values; MDSP_RESP_ANGLE: atan2(im H, re H), nw real values; MDSP_RESP_REAL_MINUS: re H - cminus, nw real
+ *   values.  in_mode MDSP_RESP_W: nw real w, the point is e^{iw}, with MDSP_RESP_NEG e^{-iw} (the device's sincos); MDSP_RESP_POINTS: nw complex points
+ *   as given (any contour; the mode in which the device equals mdsp_resp_emulate_host bit for bit for the COMPLEX and REAL_MINUS outputs).
+ *   The division is Smith's scaled one with correctly rounded real divisions; every other operation is an fma, a product, a sum or a difference
+ *   rounded once.
+ *   The cut (POLY only): the coefficients go in C chunks of L = 2^l; one launch over (tiles of 64 points x chunks) stores every chunk's Horner value
+ *   into the plan's workspace, a second forms q = y^L by l squarings per point (in double-word arithmetic, rounded once), runs Horner over the chunks in q from the highest, divides and
+ *   stores.  Store first, sum afterwards: no atomics, nothing waits, results depend on the arguments only.  chunks: 0 = automatic (C = 1 unless the
+ *   points alone leave the device empty), > 0 forced: L = the power of two >= ceil(n / chunks), at least 16, C = ceil(n / L); C == 1 is a single
+ *   launch without a workspace.  SECTIONS and ZPK are never cut (chunks is checked and otherwise ignored).
+ *   Checks, before any launch: unknown form / flags / modes, DERIV on another form than POLY, a dtype other than MDSP_F32 / F64, negative sizes,
+ *   chunks < 0, a NULL or non-finite coefficient, nden != 0 for SECTIONS, POLY without a numerator, an output that overlaps the input:
+ *   MDSP_ERR_ARGUMENT; more than 16 sections: MDSP_ERR_UNSUPPORTED.  nw == 0 succeeds without a launch.
+ *   The coefficients are copied at creation; a plan touches the device at its first exec (allocation and a blocking hipMemcpy: not inside a capture).
+ * ---------------------------------------------------------------------------------------------------- */
+enum { MDSP_RESP_POLY = 0, MDSP_RESP_SECTIONS = 1, MDSP_RESP_ZPK = 2 };
+enum { MDSP_RESP_DERIV = 1, MDSP_RESP_NEG = 2 };
+enum { MDSP_RESP_COMPLEX = 0, MDSP_RESP_ANGLE = 1, MDSP_RESP_REAL_MINUS = 2 };
+enum { MDSP_RESP_W = 0, MDSP_RESP_POINTS = 1 };
+typedef struct mdsp_resp_plan_s* mdsp_resp_plan;
+int mdsp_resp_plan_create(mdsp_resp_plan* plan, int form, int flags, int out_mode, int in_mode, int dtype, const double* num, int64_t nnum,
+                          const double* den, int64_t nden, double gain, double cminus, int64_t nw, int64_t chunks);
+int mdsp_resp_plan_destroy(mdsp_resp_plan plan);
+int mdsp_resp_plan_info(mdsp_resp_plan plan, int64_t* nchunks, int64_t* chunk_len, int64_t* workspace_bytes);
+int mdsp_resp_exec(mdsp_resp_plan plan, const void* w_or_points_dev, void* out_dev, void* stream);
+/* Pure host arithmetic, no device needed; ncoef: the longer of the two coefficient vectors.  Any output pointer may be NULL. */
+int mdsp_resp_geometry_for(int form, int dtype, int64_t ncoef, int has_den, int64_t nw, int64_t chunks, int64_t* nchunks, int64_t* chunk_len,
+                           int64_t* workspace_bytes);
+/* Host emulation of the device code (no device): the same cut, chunk order, squaring chain and operators (csrc/resp_op.h) on host arrays, POINTS input. */
+int mdsp_resp_emulate_host(const void* points_host, void* out_host, int form, int flags, int out_mode, int dtype, const double* num, int64_t nnum,
+                           const double* den, int64_t nden, double gain, double cminus, int64_t nw, int64_t chunks);
+
+/* ------------------------------------------------------------------------------------------------------
  * Deterministic reductions along one dimension (rms, rmsfft, meanfreq, finddelay of src/util.jl:186-220, :336-347).  The array is
  *   (inner, len, outer) as for unwrap, reduced along len; one result per line, line = i + inner o:
  *     MDSP_REDUCE_SUMABS2    sum |x|^2; MDSP_F32 / F64 / C32 / C64; result one Float64.  Float32 terms are formed in Float64 (exact products),

@@ -26,6 +26,7 @@ export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, td
        welch_finalize, welch_allreduce!, pin!, unpin!, MTConfig, mt_pgram, mt_pgram!, MTSpectrogramConfig, mt_spectrogram,
        mt_spectrogram!, MTCrossSpectraConfig, mt_cross_power_spectra, mt_cross_power_spectra!, MTCoherenceConfig,
        mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss, unwrap, unwrap!, sosfilt, sosfilt!,
+       resp, resp_geometry, resp_emulate, impresp, stepresp,
        rms, rmsfft, meanfreq, finddelay, shiftsignal, shiftsignal!, alignsignals, alignsignals!, pow2db, amp2db, db2pow, db2amp
 
 const lib = get(ENV, "MI355DSP_LIB", joinpath(@__DIR__, "..", "dsp.jl_amd", "libmi355dsp.so"))
@@ -549,6 +550,60 @@ function sosfilt!(y::DeviceArray{T}, coef::Matrix{Float64}, gain::Union{Nothing,
 end
 sosfilt(coef::Matrix{Float64}, gain, x::DeviceArray{T}; kwargs...) where {T<:SosTypes} = sosfilt!(DeviceArray{T}(size(x)), coef, gain, x; kwargs...)
 sosfilt(coef::Matrix{Float64}, gain, x::AbstractArray{T}; kwargs...) where {T<:SosTypes} = download(sosfilt!(upload(Array(x)), coef, gain, upload(Array(x)); kwargs...))
+
+# freqresp / phaseresp / grpdelay   Filters/response.jl:27-52, :73-76, :96-111: a rational function at nw points of the unit circle (mdsp_resp_*).
+# form RESP_POLY: num = b, den = a in powers of z^-1 (den === nothing: FIR), y = exp(-iw) with RESP_NEG; RESP_SECTIONS: num = the 5 x K table of
+# sosfilt, gain = f.g; RESP_ZPK: num / den = zeros / poles as (re, im) pairs (reinterpret(Float64, z)), gain = f.k.  T is the REAL type of the working
+# type: Float32 when coefficients and w are, Float64 otherwise.  From DSP.jl's types:
+#   freqresp(f::PolynomialRatio, w) = resp(RESP_POLY, coefb(f), coefa(f), w; flags=RESP_NEG)
+#   phaseresp                        = unwrap!(resp(...; out_mode=RESP_ANGLE))
+#   grpdelay: c = xcorr(b, a);         resp(RESP_POLY, c, c, w; flags=RESP_NEG | RESP_DERIV, out_mode=RESP_REAL_MINUS, cminus=length(a) - 1)
+const RESP_POLY, RESP_SECTIONS, RESP_ZPK = Cint(0), Cint(1), Cint(2)
+const RESP_DERIV, RESP_NEG = Cint(1), Cint(2)
+const RESP_COMPLEX, RESP_ANGLE, RESP_REAL_MINUS = Cint(0), Cint(1), Cint(2)
+const RESP_W, RESP_POINTS = Cint(0), Cint(1)
+const RespTypes = Union{Float32,Float64}
+resp_count(form, v) = v === nothing ? 0 : form == RESP_POLY ? length(v) : form == RESP_SECTIONS ? div(length(v), 5) : div(length(v), 2)
+function resp_geometry(form::Integer, ::Type{T}, ncoef::Integer, has_den::Bool, nw::Integer; chunks::Integer=0) where {T<:RespTypes}
+    C, L, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_resp_geometry_for, lib), Cint, (Cint, Cint, Int64, Cint, Int64, Int64, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                form, mdtype(T), ncoef, has_den ? 1 : 0, nw, chunks, C, L, ws))
+    (chunks=Int(C[]), chunk_len=Int(L[]), workspace_bytes=Int(ws[]))
+end
+# the host emulation of the device code (same cut, chunk order, squaring chain and operators) at given points: equal to the device bit for bit
+function resp_emulate(form::Integer, num::Array{Float64}, den::Union{Nothing,Array{Float64}}, points::Array{Complex{T}}; gain::Real=1.0, flags::Integer=0,
+                      out_mode::Integer=RESP_COMPLEX, cminus::Real=0.0, chunks::Integer=0) where {T<:RespTypes}
+    out = out_mode == RESP_COMPLEX ? similar(points) : Array{T}(undef, size(points))
+    GC.@preserve num den points out check(ccall((:mdsp_resp_emulate_host, lib), Cint,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Cint, Cint, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Cdouble, Cdouble, Int64, Int64),
+        pointer(points), pointer(out), form, flags, out_mode, mdtype(T), pointer(num), resp_count(form, num), den === nothing ? C_NULL : pointer(den),
+        resp_count(form, den), Float64(gain), Float64(cminus), length(points), chunks))
+    out
+end
+# one plan over the device array of frequencies (in_mode = RESP_W, real) or of points (RESP_POINTS, complex); the result has the shape of `arg`
+function resp(form::Integer, num::Array{Float64}, den::Union{Nothing,Array{Float64}}, arg::DeviceArray{A}; gain::Real=1.0, flags::Integer=0,
+              out_mode::Integer=RESP_COMPLEX, cminus::Real=0.0, chunks::Integer=0) where {A<:Union{Float32,Float64,ComplexF32,ComplexF64}}
+    T = real(A)
+    in_mode = A <: Complex ? RESP_POINTS : RESP_W
+    out = out_mode == RESP_COMPLEX ? DeviceArray{Complex{T}}(size(arg)) : DeviceArray{T}(size(arg))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve num den check(ccall((:mdsp_resp_plan_create, lib), Cint,
+        (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint, Ptr{Cdouble}, Int64, Ptr{Cdouble}, Int64, Cdouble, Cdouble, Int64, Int64),
+        h, form, flags, out_mode, in_mode, mdtype(T), pointer(num), resp_count(form, num), den === nothing ? C_NULL : pointer(den),
+        resp_count(form, den), Float64(gain), Float64(cminus), length(arg), chunks))
+    try
+        C, L, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_resp_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], C, L, ws))
+        check(ccall((:mdsp_resp_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), h[], arg.ptr, out.ptr, C_NULL))
+    finally
+        ccall((:mdsp_resp_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+    out
+end
+resp(form::Integer, num, den, w::AbstractArray{<:Real}; kwargs...) = download(resp(form, Float64.(num), den === nothing ? nothing : Float64.(den), upload(Array(float.(w))); kwargs...))
+# impresp / stepresp (response.jl:127-140) on a section table: filt of a Float64 impulse or step
+impresp(coef::Matrix{Float64}, gain, n::Integer=100) = sosfilt(coef, gain, setindex!(zeros(n), 1, 1))
+stepresp(coef::Matrix{Float64}, gain, n::Integer=100) = sosfilt(coef, gain, ones(n))
 
 # ---------------------------------------------------------------------------------------------- util.jl:138-220, :316-430
 # COMMON DSP TOOLS and DELAY FINDING UTILITIES: deterministic device reductions (mdsp_reduce_*: store, then sum; Float64 additions in a fixed order)
