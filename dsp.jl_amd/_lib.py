@@ -21,6 +21,7 @@ OLS_FILT, OLS_CONV = 0, 1
 UNWRAP_CONTIGUOUS, UNWRAP_STRIDED = 0, 1
 REDUCE_SUMABS2, REDUCE_SUMABS2_W, REDUCE_ABSARGMAX = 0, 1, 2
 REDUCE_CONTIGUOUS, REDUCE_STRIDED = 0, 1
+EST_SUM, EST_ABS2ARGMAX = 0, 1
 RESP_POLY, RESP_SECTIONS, RESP_ZPK = 0, 1, 2
 RESP_DERIV, RESP_NEG = 1, 2
 RESP_COMPLEX, RESP_ANGLE, RESP_REAL_MINUS = 0, 1, 2
@@ -150,6 +151,21 @@ PROTOTYPES = {
     "mdsp_reduce_exec": (ci, [vp, vp, vp, vp]),
     "mdsp_reduce_geometry_for": (ci, [i64, i64, i64, ci, ci, i64, pint, pi64, pi64, pi64, pi64]),
     "mdsp_reduce_emulate": (ci, [vp, vp, i64, i64, i64, ci, ci, cd, i64, i64, i64, pi64]),
+    "mdsp_est_reduce_plan_create": (ci, [pvp, i64, i64, i64, ci, ci, i64]),
+    "mdsp_est_reduce_plan_destroy": (ci, [vp]),
+    "mdsp_est_reduce_plan_info": (ci, [vp, pint, pi64, pi64, pi64, pi64]),
+    "mdsp_est_reduce_exec": (ci, [vp, vp, vp, vp]),
+    "mdsp_est_reduce_geometry_for": (ci, [i64, i64, i64, ci, ci, i64, pint, pi64, pi64, pi64, pi64]),
+    "mdsp_est_reduce_emulate": (ci, [vp, vp, i64, i64, i64, ci, ci, i64, i64, pi64]),
+    "mdsp_est_peak_gather": (ci, [vp, i64, i64, ci, ci, vp, vp, vp]),
+    "mdsp_est_peak_emulate": (ci, [vp, i64, i64, ci, ci, vp, vp]),
+    "mdsp_quinn_plan_create": (ci, [pvp, ci, i64, i64]),
+    "mdsp_quinn_plan_destroy": (ci, [vp]),
+    "mdsp_quinn_plan_info": (ci, [vp, pi64, pi64, pi64, pi64, pi64]),
+    "mdsp_quinn_pass_exec": (ci, [vp, vp, pdbl, cd, vp, vp]),
+    "mdsp_quinn_geometry_for": (ci, [ci, i64, i64, pi64, pi64, pi64, pi64, pi64]),
+    "mdsp_quinn_pass_emulate_host": (ci, [vp, ci, i64, i64, pdbl, cd, pdbl]),
+    "mdsp_quinn_estimate": (ci, [vp, vp, cd, cd, cd, i64, pdbl, pint, pi64, vp]),
     "mdsp_shift_plan_create": (ci, [pvp, i64, i64, i64, ci, i64, ci]),
     "mdsp_shift_plan_destroy": (ci, [vp]),
     "mdsp_shift_plan_info": (ci, [vp, pint, pi64, pi64, pi64, pi64]),

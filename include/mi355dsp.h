@@ -471,6 +471,71 @@ int mdsp_reduce_emulate(const void* in_host, void* out_host, int64_t inner, int6
                         int64_t centre, int64_t segments, int64_t phase, int64_t* depth_reached);
 
 /* ------------------------------------------------------------------------------------------------------
+ * jacobsen and quinn (src/estimation.jl:93-220): the frequency of the largest sinusoid in a vector (csrc/estimation.hip).
+ *
+ * Reductions (csrc/est_op.h: operators for the templates, the cut and the order of additions of the reductions above; the operator numbers of
+ * mdsp_reduce_* are not extended).  Arguments, routes, segments, phase and depth as for mdsp_reduce_*:
+ *     MDSP_EST_SUM          the Float64 sum of a line, every element converted exactly; MDSP_F32 / F64: one Float64, MDSP_C32 / C64: two (re, im).
+ *     MDSP_EST_ABS2ARGMAX   complex bins X_k: two Int64, (index, flag).  The largest |X_k|^2 -- formed in Float64 as SUMABS2 forms it -- wins, at
+ *                           equal value the smaller index (findmax's first maximum).  A bin whose |X|^2 is NaN does not compete and sets flag = 1;
+ *                           a line without a candidate gives index -1.
+ *   mdsp_est_peak_gather: from the bins of one transform of n >= 2 samples (onesided: nbins = n / 2 + 1 bins, else nbins = n) and an ABS2ARGMAX result,
+ *   one record of eight 8-byte words {index, flag, X[k-1], X[k], X[k+1]} (the bins as (re, im) in Float64), with the reference's wrap-around
+ *   (estimation.jl:98-103) for a full transform and the Hermitian mirror at the ends of a one-sided one (X[-1] = conj(X[1]); beyond the last bin
+ *   X[k+1] = conj(X[n-k-1])).  index -1: the bins are written as zeros.  One launch of one lane; mdsp_est_peak_emulate runs the same text on host arrays.
+ *
+ * quinn: one PASS of the iteration is a linear recurrence over the signal whose result is a record of a few sums; the filtered signal is never
+ * stored.  State and arithmetic are Float64 for every dtype; the mean is removed at the load, d_t = (double)x_t - mean, one rounding.
+ *     MDSP_F32 / F64 (Quinn & Fernandes, :175-182), param = alpha:  xi_t = d_t + fma(alpha, xi_(t-1), -xi_(t-2)) from a zero state (at t = 2 one
+ *         rounding more than the reference's muladd); record of four doubles {sum_(t=3..n) (xi_t + xi_(t-2)) xi_(t-1), sum_(t=1..n-1) xi_t^2, xi_1, xi_2}.
+ *     MDSP_C32 / C64 (Quinn, :205-212), param = omega:  xi_t = d_t + cis(omega) xi_(t-1); record of three doubles
+ *         {re S, im S, sum_(t=1..n-1) |xi_t|^2}, S = sum_(t=2..n) d_t conj(xi_(t-1)).
+ *   Given the state at its first sample every run of 16 samples is computed by exactly that serial recurrence; a scan with powers of the
+ *   recurrence's matrix (host, long double, rounded once, passed in the kernel arguments: no copy per iteration) supplies the start states
+ *   (csrc/quinn_scan.h, which also fixes every rounding and the order of every addition).  segments as for mdsp_sos_*: 0 = automatic, > 0 forced
+ *   (ceil(n / segments) samples each, clamped to n); S == 1 is one launch, S > 1 four (end states, carries, sums, finish) with 32 (complex: 40) bytes of
+ *   workspace per segment.  tile = 64 run samples.  No atomics, nothing waits: a record depends on the arguments only and equals
+ *   mdsp_quinn_pass_emulate_host bit for bit.  mean: two doubles (re, im; im ignored for a real dtype).
+ *   mdsp_quinn_estimate is the whole algorithm: the mean (one MDSP_EST_SUM reduction), then the reference's iteration and stopping rule; per iteration
+ *   one pass, one copy of the record and one synchronisation of `stream`.  estimate in Hz, reached_maxiters as the reference's second result,
+ *   iterations (may be NULL) the passes run.  A parameter that is not finite gives a NaN record without a launch, so a NaN runs to maxiters and returns
+ *   (NaN, 1) as in the reference.
+ *   Checks, before any launch: a bad dtype, n < 2, segments < 0, NULL or misaligned buffers: MDSP_ERR_ARGUMENT.  Powers that are not finite in
+ *   Float64 (an iterate with |alpha| > 2 on a long signal): MDSP_ERR_UNSUPPORTED.  A final |beta| > 2 (the reference's acos throws): MDSP_ERR_DOMAIN.
+ *   A plan touches the device at its first exec (allocations: not inside a stream capture); mdsp_quinn_estimate synchronises and cannot be captured.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { MDSP_EST_SUM = 0, MDSP_EST_ABS2ARGMAX = 1 };
+typedef struct mdsp_est_reduce_plan_s* mdsp_est_reduce_plan;
+int mdsp_est_reduce_plan_create(mdsp_est_reduce_plan* plan, int64_t inner, int64_t len, int64_t outer, int op, int dtype, int64_t segments);
+int mdsp_est_reduce_plan_destroy(mdsp_est_reduce_plan plan);
+int mdsp_est_reduce_plan_info(mdsp_est_reduce_plan plan, int* route, int64_t* nsegments, int64_t* seglen, int64_t* depth, int64_t* workspace_bytes);
+/* out_dev: 8 bytes (SUM of a real line) or 16 bytes per line, 8-byte aligned. */
+int mdsp_est_reduce_exec(mdsp_est_reduce_plan plan, const void* in_dev, void* out_dev, void* stream);
+/* Pure host arithmetic, no device needed.  Any output pointer may be NULL. */
+int mdsp_est_reduce_geometry_for(int64_t inner, int64_t len, int64_t outer, int op, int dtype, int64_t segments, int* route, int64_t* nsegments,
+                                 int64_t* seglen, int64_t* depth, int64_t* workspace_bytes);
+/* Host emulation of the device code (no device). */
+int mdsp_est_reduce_emulate(const void* in_host, void* out_host, int64_t inner, int64_t len, int64_t outer, int op, int dtype, int64_t segments,
+                            int64_t phase, int64_t* depth_reached);
+/* dtype: MDSP_C32 / C64 of the bins; argmax: the two Int64 of an ABS2ARGMAX result; out: 64 bytes, 8-byte aligned. */
+int mdsp_est_peak_gather(const void* bins_dev, int64_t nbins, int64_t n, int onesided, int dtype, const void* argmax_dev, void* out_dev, void* stream);
+int mdsp_est_peak_emulate(const void* bins_host, int64_t nbins, int64_t n, int onesided, int dtype, const void* argmax_host, void* out_host);
+
+typedef struct mdsp_quinn_plan_s* mdsp_quinn_plan;
+int mdsp_quinn_plan_create(mdsp_quinn_plan* plan, int dtype, int64_t n, int64_t segments);
+int mdsp_quinn_plan_destroy(mdsp_quinn_plan plan);
+int mdsp_quinn_plan_info(mdsp_quinn_plan plan, int64_t* nsegments, int64_t* seglen, int64_t* tile, int64_t* run, int64_t* workspace_bytes);
+/* One pass.  out_dev: four doubles (real dtype) or three (complex), 8-byte aligned. */
+int mdsp_quinn_pass_exec(mdsp_quinn_plan plan, const void* x_dev, const double* mean, double param, void* out_dev, void* stream);
+/* Pure host arithmetic, no device needed.  Any output pointer may be NULL. */
+int mdsp_quinn_geometry_for(int dtype, int64_t n, int64_t segments, int64_t* nsegments, int64_t* seglen, int64_t* tile, int64_t* run,
+                            int64_t* workspace_bytes);
+/* Host emulation of one pass (no device): the same cut, tiles, scan order, arithmetic and order of additions (csrc/quinn_scan.h) on a host array. */
+int mdsp_quinn_pass_emulate_host(const void* x_host, int dtype, int64_t n, int64_t segments, const double* mean, double param, double* out_host);
+int mdsp_quinn_estimate(mdsp_quinn_plan plan, const void* x_dev, double f0, double fs, double tol, int64_t maxiters, double* estimate,
+                        int* reached_maxiters, int64_t* iterations, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * shiftsignal / shiftsignal! (src/util.jl:357-395): y[i] = x[i - s] where that exists, else 0, one line of l elements of 4, 8 or 16 bytes
  *   (moved as words: any element type).  in_place: out is the input.  Routes, chosen at plan creation and reported:
  *     MDSP_SHIFT_DISJOINT  out of place, or in place with 2 |s| >= l; one launch

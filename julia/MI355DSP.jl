@@ -27,7 +27,8 @@ export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, td
        mt_spectrogram!, MTCrossSpectraConfig, mt_cross_power_spectra, mt_cross_power_spectra!, MTCoherenceConfig,
        mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss, unwrap, unwrap!, sosfilt, sosfilt!,
        resp, resp_geometry, resp_emulate, impresp, stepresp,
-       rms, rmsfft, meanfreq, finddelay, shiftsignal, shiftsignal!, alignsignals, alignsignals!, pow2db, amp2db, db2pow, db2amp
+       rms, rmsfft, meanfreq, finddelay, shiftsignal, shiftsignal!, alignsignals, alignsignals!, pow2db, amp2db, db2pow, db2amp,
+       jacobsen, quinn, quinn_geometry, quinn_pass_emulate
 
 const lib = get(ENV, "MI355DSP_LIB", joinpath(@__DIR__, "..", "dsp.jl_amd", "libmi355dsp.so"))
 
@@ -691,6 +692,113 @@ function finddelay(x::AbstractVector{<:Real}, y::AbstractVector{<:Real})
     (rec[2] != 0 || rec[1] < 0) && throw(ArgumentError("finddelay: the cross-correlation holds NaN"))
     centre - Int(rec[1])
 end
+
+# ---------------------------------------------------------------------------------------------- estimation.jl:93-220
+# jacobsen and quinn: one transform, ABS2ARGMAX and a 64-byte peak record; per quinn iteration one pass over the signal that leaves a record of a few
+# Float64 sums (mdsp_quinn_*; the filtered signal is never stored).  esprit is not accelerated (a dense SVD).
+const EST_SUM, EST_ABS2ARGMAX = Cint(0), Cint(1)
+
+function est_reduce_geometry(inner::Integer, len::Integer, outer::Integer, op::Integer, ::Type{T}; segments::Integer=0) where {T}
+    route, S, seglen, depth, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_est_reduce_geometry_for, lib), Cint, (Int64, Int64, Int64, Cint, Cint, Int64, Ref{Cint}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                inner, len, outer, op, mdtype(T), segments, route, S, seglen, depth, ws))
+    (route=Int(route[]), segments=Int(S[]), seglen=Int(seglen[]), depth=Int(depth[]), workspace_bytes=Int(ws[]))
+end
+# the host emulation of the device code: Float64 sums (1 per real line, 2 per complex line) or Int64 (index, flag)
+function est_reduce_emulate(x::Array{T}, inner::Integer, len::Integer, outer::Integer, op::Integer; segments::Integer=0, phase::Integer=0) where {T}
+    words = (op == EST_SUM && T <: Real) ? 1 : 2
+    out = op == EST_ABS2ARGMAX ? zeros(Int64, words, inner * outer) : zeros(Float64, words, inner * outer)
+    reached = Ref{Int64}(0)
+    GC.@preserve x out check(ccall((:mdsp_est_reduce_emulate, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Int64, Cint, Cint, Int64, Int64, Ref{Int64}),
+                                   pointer(x), pointer(out), inner, len, outer, op, mdtype(T), segments, phase, reached))
+    out, Int(reached[])
+end
+function est_reduce_exec!(out::DeviceArray, x::DeviceArray{T}, inner::Integer, len::Integer, outer::Integer, op::Integer; segments::Integer=0) where {T}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_est_reduce_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Int64, Int64, Int64, Cint, Cint, Int64), h, inner, len, outer, op, mdtype(T), segments))
+    try
+        route, S, seglen, depth, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_est_reduce_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], route, S, seglen, depth, ws))
+        check(ccall((:mdsp_est_reduce_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), h[], x.ptr, out.ptr, C_NULL))
+    finally
+        ccall((:mdsp_est_reduce_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+    out
+end
+# the peak record on the host, from host bins and an (index, flag) pair: the text of the device's gather
+function est_peak_emulate(bins::Vector{T}, n::Integer, onesided::Bool, argmax::Vector{Int64}) where {T<:Union{ComplexF32,ComplexF64}}
+    out = zeros(Int64, 8)
+    GC.@preserve bins argmax out check(ccall((:mdsp_est_peak_emulate, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}),
+                                             pointer(bins), length(bins), n, onesided, mdtype(T), pointer(argmax), pointer(out)))
+    out
+end
+
+# jacobsen(x, Fs)   :93-115.  Half a spectrum is enough for a real signal: a peak in the upper half gives the same value after abs.
+function jacobsen(x::AbstractVector{T}, Fs::Real=1.0) where {T<:Number}
+    N = length(x)
+    N >= 2 || throw(ArgumentError("jacobsen: at least two samples are needed (got $N)"))
+    onesided = T <: Real
+    X = stft(x, N, 0; nfft=N, window=nothing, onesided=onesided)
+    bins = X isa DeviceArray ? X : upload(vec(Array(X)))
+    rec = DeviceArray{Int64}((10,))                              # (index, flag), then the 64-byte peak record
+    est_reduce_exec!(rec, bins, 1, length(bins), 1, EST_ABS2ARGMAX)
+    check(ccall((:mdsp_est_peak_gather, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                bins.ptr, length(bins), N, onesided, mdtype(eltype(bins)), rec.ptr, rec.ptr + 16, C_NULL))
+    r = download(rec)
+    k, flag = r[3], r[4]
+    (flag != 0 || k < 0) && return NaN
+    Xm, X0, Xp = reinterpret(ComplexF64, r[5:10])
+    fpeak = (k < (N + 1) >> 1 ? k : k - N) * (Fs / N)           # fftfreq(N, Fs)[k + 1]
+    δ = -real((Xp - Xm) / (2X0 - Xm - Xp))                       # :108
+    estimate = fpeak + δ * Fs / N
+    onesided ? abs(estimate) : estimate
+end
+
+function quinn_geometry(::Type{T}, n::Integer; segments::Integer=0) where {T}
+    S, seglen, tile, run, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_quinn_geometry_for, lib), Cint, (Cint, Int64, Int64, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), mdtype(T), n, segments, S, seglen, tile, run, ws))
+    (segments=Int(S[]), seglen=Int(seglen[]), tile=Int(tile[]), run=Int(run[]), workspace_bytes=Int(ws[]))
+end
+# the host emulation of one pass: {num, den, xi_1, xi_2} for a real signal (param = alpha), {re S, im S, den} for a complex one (param = omega)
+function quinn_pass_emulate(x::Vector{T}, mean::Number, param::Real; segments::Integer=0) where {T}
+    out = zeros(Float64, 4)
+    mu = Float64[real(mean), imag(mean)]
+    GC.@preserve x mu out check(ccall((:mdsp_quinn_pass_emulate_host, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Cdouble}, Cdouble, Ptr{Cdouble}),
+                                      pointer(x), mdtype(T), length(x), segments, pointer(mu), Float64(param), pointer(out)))
+    T <: Real ? out : out[1:3]
+end
+function quinn_pass!(out::DeviceArray{Float64}, x::DeviceArray{T}, mean::Number, param::Real; segments::Integer=0) where {T}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_quinn_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Cint, Int64, Int64), h, mdtype(T), length(x), segments))
+    mu = Float64[real(mean), imag(mean)]
+    try
+        S, seglen, tile, run, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_quinn_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], S, seglen, tile, run, ws))
+        GC.@preserve mu check(ccall((:mdsp_quinn_pass_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Cdouble, Ptr{Cvoid}, Ptr{Cvoid}),
+                                    h[], x.ptr, pointer(mu), Float64(param), out.ptr, C_NULL))
+    finally
+        ccall((:mdsp_quinn_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+    out
+end
+
+# quinn(x, f0, Fs; tol, maxiters)   :157-220: the mean, the iteration and the stopping rule run in the library (mdsp_quinn_estimate)
+function quinn(x::DeviceArray{T,1}, f0::Real, Fs::Real; tol=1e-6, maxiters::Integer=20) where {T<:Union{Float32,Float64,ComplexF32,ComplexF64}}
+    length(x) >= 2 || throw(ArgumentError("quinn: at least two samples are needed (got $(length(x)))"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_quinn_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Cint, Int64, Int64), h, mdtype(T), length(x), 0))
+    est, reached, iters = Ref{Cdouble}(0), Ref{Cint}(0), Ref{Int64}(0)
+    try
+        check(ccall((:mdsp_quinn_estimate, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Int64, Ref{Cdouble}, Ref{Cint}, Ref{Int64}, Ptr{Cvoid}),
+                    h[], x.ptr, Float64(f0), Float64(Fs), Float64(tol), maxiters, est, reached, iters, C_NULL))
+    finally
+        ccall((:mdsp_quinn_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+    est[], reached[] != 0
+end
+quinn(x::AbstractVector{T}, f0::Real, Fs::Real; kwargs...) where {T<:Number} = quinn(upload(convert(Vector{fftintype(T)}, x)), f0, Fs; kwargs...)
+quinn(x::AbstractVector; kwargs...) = quinn(x, jacobsen(x, 1.0), 1.0; kwargs...)              # :153
+quinn(x::AbstractVector, Fs::Real; kwargs...) = quinn(x, jacobsen(x, Fs), Fs; kwargs...)      # :155
 
 function shift_geometry(l::Integer, s::Integer, elem_bytes::Integer, in_place::Bool; tile::Integer=0, route::Integer=SHIFT_AUTO)
     r, t, c, n, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
