@@ -2741,18 +2741,60 @@ int arb_scan_device(mdsp_firarb_s* f, const ArbStep& step, int64_t xlen, int64_t
     return MDSP_OK;
 }
 
-template <typename XS, typename A, typename R, int NCH> int arb_launch_n(mdsp_firarb_s* f, ArbArgs& a, int tile, int64_t span, hipStream_t st) {
-    const int64_t taps_bytes = 2 * (int64_t)f->base.tp * f->nphi * (int64_t)sizeof(R);
-    a.tile = tile;
-    a.span = (int)span;
-    const size_t lds_bytes = arb_rec_bytes(tile) + (size_t)span * NCH * sizeof(A) + (a.taps_in_lds ? (size_t)taps_bytes : 0);
-    auto kern = arbitrary_fir_kernel<XS, A, R, NCH>;
-    if (lds_bytes > 48 * 1024) MDSP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+// Every launch decision of the arbitrary-rate kernel, as pure host arithmetic: mdsp_firarb_exec launches with exactly what this returns,
+// and mdsp_arb_kernel_geometry reports it (the tests assert on it which path a case runs).  real_bytes = sizeof(R) of the arithmetic,
+// acc_bytes = sizeof(A) of one sample in it.
+struct ArbGeometry {
+    int tile;         // outputs per workgroup
+    int64_t span;     // staged samples per tile and channel (0: the windows are read straight from global memory)
+    int nchg;         // channels per group (the NCH instantiation: 4, 2 or 1)
+    int64_t groups, tiles;
+    unsigned gy;      // grid rows; gy < groups: a workgroup loops over several channel groups
+    bool taps_in_lds;
+    size_t lds_bytes;
+};
+ArbGeometry arb_geometry(int64_t tp, int64_t nphi, double delta, int64_t real_bytes, int64_t acc_bytes, int64_t nch, int64_t nout, int cu_count) {
+    ArbGeometry g{};
+    const int64_t taps_bytes = 2 * tp * nphi * real_bytes;
+    g.taps_in_lds = taps_bytes <= 32 * 1024;
+    const int nch_max = tunables().arb_nch;   // tuning knob
+    // channels per group: the most whose workgroup (trajectory records + interleaved input span of tile * Delta / Nphi + tp
+    // samples per channel + tap pairs) stays within 44 KiB of LDS, i.e. leaves >= 3 workgroups per CU; measured on MI355X,
+    // larger footprints lose more to occupancy than the shared tap reads save
+    int nchg = nch >= 3 ? 4 : (int)std::max<int64_t>(1, nch);
+    nchg = std::min(nchg, nch_max >= 4 ? 4 : nch_max >= 2 ? 2 : 1);
+    int tile = 1024;
+    if (tunables().arb_tile > 0) tile = std::min(64 * ARB_BLK, std::max(ARB_BLK, tunables().arb_tile / ARB_BLK * ARB_BLK));   // tuning knob (one wave replays the tile)
+    const int tile0 = tile;
+    int64_t span = 0;
+    const auto span_of = [&](int t) { return ((int64_t)std::ceil((double)t * delta / (double)nphi) + tp + 4 + 3) & ~int64_t(3); };   // multiple of 4: the tap pairs that follow stay 16-byte aligned
+    const int64_t fixed = (int64_t)arb_rec_bytes(tile0) + (g.taps_in_lds ? taps_bytes : 0);
+    span = span_of(tile);
+    while (nchg > 1 && fixed + span * nchg * acc_bytes > 44 * 1024) nchg /= 2;
+    if (nchg == 1) {   // one channel at a time: shrink the tile until its span fits 48 KiB
+        while ((span = span_of(tile)) * acc_bytes > 48 * 1024 && tile > ARB_BLK) tile /= 2;
+        if (span * acc_bytes > 48 * 1024) span = 0;   // very low rates: outputs are far apart, read through L2 instead
+    }
+    g.tile = tile;
+    g.span = span;
+    g.nchg = nchg;
+    g.lds_bytes = arb_rec_bytes(tile) + (size_t)span * nchg * (size_t)acc_bytes + (g.taps_in_lds ? (size_t)taps_bytes : 0);
     // channels share a tile's replayed trajectory (and, NCH at a time, its tap reads): loop over the channel groups inside the
     // workgroup unless there are too few tiles to fill the GPU
-    const int64_t tiles = cdiv(a.nout, tile);
-    const int64_t groups = cdiv(f->base.nch, NCH);
-    const unsigned gy = (unsigned)std::min<int64_t>(groups, std::max<int64_t>(1, cdiv((int64_t)device_cu_count() * 8, tiles)));
+    g.tiles = cdiv(nout, tile);
+    g.groups = cdiv(nch, nchg);
+    g.gy = (unsigned)std::min<int64_t>(g.groups, std::max<int64_t>(1, cdiv((int64_t)cu_count * 8, std::max<int64_t>(1, g.tiles))));
+    return g;
+}
+
+template <typename XS, typename A, typename R, int NCH> int arb_launch_n(mdsp_firarb_s* f, ArbArgs& a, const ArbGeometry& g, hipStream_t st) {
+    a.tile = g.tile;
+    a.span = (int)g.span;
+    const size_t lds_bytes = g.lds_bytes;
+    auto kern = arbitrary_fir_kernel<XS, A, R, NCH>;
+    if (lds_bytes > 48 * 1024) MDSP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    const int64_t tiles = g.tiles;
+    const unsigned gy = g.gy;
     const dim3 grid((unsigned)tiles, gy);
     const bool prof = MDSP_DBG(arb_prof) && gy == 1;
     if (prof) {
@@ -2782,32 +2824,14 @@ template <typename XS, typename A, typename R, int NCH> int arb_launch_n(mdsp_fi
 }
 
 template <typename XS, typename A, typename R> int arb_launch(mdsp_firarb_s* f, ArbArgs& a, hipStream_t st) {
-    const int64_t taps_bytes = 2 * (int64_t)f->base.tp * f->nphi * (int64_t)sizeof(R);
-    a.taps_in_lds = taps_bytes <= 32 * 1024;
+    const ArbGeometry g = arb_geometry(f->base.tp, f->nphi, f->delta, (int64_t)sizeof(R), (int64_t)sizeof(A), f->base.nch, a.nout, device_cu_count());
+    a.taps_in_lds = g.taps_in_lds;
     a.ablate = MDSP_DBG(ablate);
     a.prio = tunables().arb_prio;
-    const int nch_max = tunables().arb_nch;   // tuning knob
-    // channels per group: the most whose workgroup (trajectory records + interleaved input span of tile * Delta / Nphi + tp
-    // samples per channel + tap pairs) stays within 44 KiB of LDS, i.e. leaves >= 3 workgroups per CU; measured on MI355X,
-    // larger footprints lose more to occupancy than the shared tap reads save
-    int nchg = f->base.nch >= 3 ? 4 : (int)std::max<int64_t>(1, f->base.nch);
-    nchg = std::min(nchg, nch_max >= 4 ? 4 : nch_max >= 2 ? 2 : 1);
-    int tile = 1024;
-    if (tunables().arb_tile > 0) tile = std::min(64 * ARB_BLK, std::max(ARB_BLK, tunables().arb_tile / ARB_BLK * ARB_BLK));   // tuning knob (one wave replays the tile)
-    const int tile0 = tile;
-    int64_t span = 0;
-    const auto span_of = [&](int t) { return ((int64_t)std::ceil((double)t * f->delta / (double)f->nphi) + f->base.tp + 4 + 3) & ~int64_t(3); };   // multiple of 4: the tap pairs that follow stay 16-byte aligned
-    const int64_t fixed = (int64_t)arb_rec_bytes(tile0) + (a.taps_in_lds ? taps_bytes : 0);
-    span = span_of(tile);
-    while (nchg > 1 && fixed + span * nchg * (int64_t)sizeof(A) > 44 * 1024) nchg /= 2;
-    if (nchg == 1) {   // one channel at a time: shrink the tile until its span fits 48 KiB
-        while ((span = span_of(tile)) * (int64_t)sizeof(A) > 48 * 1024 && tile > ARB_BLK) tile /= 2;
-        if (span * (int64_t)sizeof(A) > 48 * 1024) span = 0;   // very low rates: outputs are far apart, read through L2 instead
-    }
-    switch (nchg) {
-        case 4: return arb_launch_n<XS, A, R, 4>(f, a, tile, span, st);
-        case 2: return arb_launch_n<XS, A, R, 2>(f, a, tile, span, st);
-        default: return arb_launch_n<XS, A, R, 1>(f, a, tile, span, st);
+    switch (g.nchg) {
+        case 4: return arb_launch_n<XS, A, R, 4>(f, a, g, st);
+        case 2: return arb_launch_n<XS, A, R, 2>(f, a, g, st);
+        default: return arb_launch_n<XS, A, R, 1>(f, a, g, st);
     }
 }
 
@@ -2821,15 +2845,17 @@ int arb_dispatch(mdsp_firarb_s* f, ArbArgs& a, hipStream_t st) {
     }
 }
 
+// (at least 16 bytes, zeroed: the arbitrary-rate kernel's tap copy loads the table in 16-byte units, and one Float32 pair is 8)
 int upload_bank(DevBuf& buf, const std::vector<double>& pd, bool as_double) {
+    const size_t bytes = (as_double ? sizeof(double) : sizeof(float)) * pd.size();
+    MDSP_TRY(buf.reserve(std::max<size_t>(16, bytes)));
+    if (bytes < 16) MDSP_HIP(hipMemset(buf.p, 0, 16));
     if (as_double) {
-        MDSP_TRY(buf.reserve(sizeof(double) * pd.size()));
-        MDSP_HIP(hipMemcpy(buf.p, pd.data(), sizeof(double) * pd.size(), hipMemcpyHostToDevice));
+        MDSP_HIP(hipMemcpy(buf.p, pd.data(), bytes, hipMemcpyHostToDevice));
     } else {
         std::vector<float> pf(pd.size());
         for (size_t i = 0; i < pd.size(); ++i) pf[i] = (float)pd[i];
-        MDSP_TRY(buf.reserve(sizeof(float) * pf.size()));
-        MDSP_HIP(hipMemcpy(buf.p, pf.data(), sizeof(float) * pf.size(), hipMemcpyHostToDevice));
+        MDSP_HIP(hipMemcpy(buf.p, pf.data(), bytes, hipMemcpyHostToDevice));
     }
     return MDSP_OK;
 }
@@ -2906,6 +2932,21 @@ int mdsp_arb_replay_check(double phi_acc, double rate, int64_t nphi, int64_t nst
         }
     }
     *mismatches = bad;
+    return MDSP_OK;
+}
+
+int mdsp_arb_kernel_geometry(int64_t taps_per_phase, int64_t nphi, double rate, int taps_dtype, int x_dtype, int64_t nch, int64_t nout, int cu_count,
+                             int64_t out8[8]) {
+    if (taps_per_phase < 1 || taps_per_phase > (int64_t(1) << 30) || nphi < 1 || nphi > (int64_t(1) << 20) || !(rate > 0.0) || nch < 1 || nch > 65535 || nout < 0)
+        MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid geometry arguments");
+    if (taps_dtype != MDSP_F32 && taps_dtype != MDSP_F64) MDSP_FAIL(MDSP_ERR_UNSUPPORTED, "FIRArbitrary takes real Float32/Float64 taps only");
+    if (!dtype_valid(x_dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid x dtype");
+    if (!out8) MDSP_FAIL(MDSP_ERR_ARGUMENT, "NULL result pointer");
+    const bool dbl = (taps_dtype == MDSP_F64) || dtype_is_double(x_dtype);   // the arithmetic mdsp_firarb_create chooses
+    const int64_t rb = dbl ? 8 : 4, ab = dtype_is_complex(x_dtype) ? 2 * rb : rb;
+    const ArbGeometry g = arb_geometry(taps_per_phase, nphi, (double)nphi / rate, rb, ab, nch, nout, cu_count > 0 ? cu_count : device_cu_count());
+    const int64_t o[8] = {g.tile, g.span, g.nchg, g.groups, g.tiles, (int64_t)g.gy, g.taps_in_lds ? 1 : 0, (int64_t)g.lds_bytes};
+    std::copy(o, o + 8, out8);
     return MDSP_OK;
 }
 

@@ -679,6 +679,14 @@ int mdsp_arb_trajectory_scan(double phi_acc, int64_t input_deficit, double rate,
 int mdsp_firarb_scan_stats(mdsp_firarb f, int64_t* scanned, int64_t* serial);
 /* test helper (host): updates at which the device replay's branch-free form of update! differs from the reference form */
 int mdsp_arb_replay_check(double phi_acc, double rate, int64_t nphi, int64_t nsteps, int64_t* mismatches);
+/* The launch geometry mdsp_firarb_exec uses for a filter of taps_per_phase x nphi taps at `rate`, nch channels and a chunk of nout outputs:
+ * the very host function the launch calls, so what it reports is what runs.  out8 = {tile (outputs per workgroup), span (staged samples per
+ * tile and channel; 0: windows read straight from memory), nchg (channels per group: the 4 / 2 / 1 instantiation), groups = ceil(nch / nchg),
+ * tiles = ceil(nout / tile), gy (grid rows; gy < groups: each workgroup loops over several channel groups), taps_in_lds (0: tap pairs read from
+ * global memory, above 32 KiB of pairs), lds_bytes (dynamic LDS per workgroup)}.  Honours the MDSP_ARB_TILE / MDSP_ARB_NCH knobs.
+ * cu_count <= 0: the current device's compute units; with cu_count > 0 it is pure host arithmetic (no device).  Diagnostics / tests. */
+int mdsp_arb_kernel_geometry(int64_t taps_per_phase, int64_t nphi, double rate, int taps_dtype, int x_dtype, int64_t nch,
+                             int64_t nout, int cu_count, int64_t out8[8]);
 
 /* ------------------------------------------------------------------------------------------------------
  * N-dimensional convolution: conv(u, v) / conv!(out, u, v) for arrays (dspbase.jl:709-792).

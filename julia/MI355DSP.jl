@@ -1439,6 +1439,13 @@ function arb_replay_check(ϕAcc::Real, rate::Real, Nϕ::Integer, nsteps::Integer
     m = Ref{Int64}(0)
     check(ccall((:mdsp_arb_replay_check, lib), Cint, (Cdouble, Cdouble, Int64, Int64, Ref{Int64}), ϕAcc, rate, Nϕ, nsteps, m)); Int(m[])
 end
+# the launch geometry of the arbitrary-rate kernel (the host function the launch itself calls; cu <= 0: the current device's compute units)
+function arb_kernel_geometry(tapsPerϕ::Integer, Nϕ::Integer, rate::Real, ::Type{Th}, ::Type{Tx}, nch::Integer, nout::Integer, cu::Integer=0) where {Th,Tx}
+    o = zeros(Int64, 8)
+    GC.@preserve o check(ccall((:mdsp_arb_kernel_geometry, lib), Cint, (Int64, Int64, Cdouble, Cint, Cint, Int64, Int64, Cint, Ptr{Int64}),
+                               tapsPerϕ, Nϕ, rate, mdtype(Th), mdtype(Tx), nch, nout, cu, pointer(o)))
+    (tile = Int(o[1]), span = Int(o[2]), nchg = Int(o[3]), groups = Int(o[4]), tiles = Int(o[5]), gy = Int(o[6]), taps_in_lds = o[7] != 0, lds_bytes = Int(o[8]))
+end
 
 # ---------------------------------------------------------------------------------------------- DF2TFilter (FIR) and filtfilt
 # DF2TFilter(PolynomialRatio(b, [1]))   Filters/filt.jl:122-181: the TDF-II register file `state` (length(b) - 1, columns) is carried between calls
