@@ -166,6 +166,12 @@ PROTOTYPES = {
     "mdsp_quinn_geometry_for": (ci, [ci, i64, i64, pi64, pi64, pi64, pi64, pi64]),
     "mdsp_quinn_pass_emulate_host": (ci, [vp, ci, i64, i64, pdbl, cd, pdbl]),
     "mdsp_quinn_estimate": (ci, [vp, vp, cd, cd, cd, i64, pdbl, pint, pi64, vp]),
+    "mdsp_burg_plan_create": (ci, [pvp, ci, i64, i64]),
+    "mdsp_burg_plan_destroy": (ci, [vp]),
+    "mdsp_burg_plan_info": (ci, [vp, pi64, pi64, pi64, pi64]),
+    "mdsp_burg_exec": (ci, [vp, vp, i64, vp, vp]),
+    "mdsp_burg_geometry_for": (ci, [ci, i64, i64, pi64, pi64, pi64, pi64]),
+    "mdsp_burg_emulate_host": (ci, [vp, ci, i64, i64, i64, vp]),
     "mdsp_shift_plan_create": (ci, [pvp, i64, i64, i64, ci, i64, ci]),
     "mdsp_shift_plan_destroy": (ci, [vp]),
     "mdsp_shift_plan_info": (ci, [vp, pint, pi64, pi64, pi64, pi64]),

@@ -536,6 +536,34 @@ int mdsp_quinn_estimate(mdsp_quinn_plan plan, const void* x_dev, double f0, doub
                         int* reached_maxiters, int64_t* iterations, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * arburg / lpc(x, p, LPCBurg()) (src/lpc.jl:28-32, :53-92): Burg's method on one vector of n samples of dtype F (R its real type), as p lattice
+ *   passes over two work arrays of n elements of F that the plan owns (csrc/lpc.hip, csrc/burg_op.h).  Neither array moves: at order m
+ *   element i of ef pairs with element i + m of eb.  On one stream, without a host round trip: a pass over x that leaves the partials of dot(x, x) and
+ *   of the order-1 inner product; then for m = 1 .. p a finish (one wavefront: folds the partials in a fixed order, adds the products at the segment
+ *   boundaries, takes the scalar step in F / R) and, for m < p, a sweep (the element-wise update fused with the partials of the order-(m+1) inner
+ *   product).  2 p launches (p = 0: two).  The partial sums are Float64, stored and summed in a fixed order: no atomics, nothing waits, and a record
+ *   depends on (x, p, the cut) only and equals mdsp_burg_emulate_host bit for bit.  x is never written.
+ *   The record: 2 p + 2 elements of F -- a[0 .. p] (a[0] = 1), the p reflection coefficients, prediction_err in the real part of the last element
+ *   (complex F: its imaginary part is 0).  record_dev is aligned to sizeof(F).
+ *   segments: 0 = automatic, > 0 forced: the cut of the pair range [0, n - 1) into ceil((n - 1) / segments) pairs each, fixed for all orders.
+ *   tile = 64 x (16 / sizeof(F)) pairs.  workspace_bytes: the two arrays, 24 bytes per segment, the state.
+ *   Checks, before any launch: a bad dtype, n < 1, segments < 0, p < 0 or p > n - 1, NULL or misaligned buffers: MDSP_ERR_ARGUMENT.  (The reference
+ *   accepts p = n and divides zero by zero there.)  A plan touches the device at its first exec (allocations: not inside a stream capture).
+ *   The work arrays, the partials and the state belong to the PLAN: one exec of a plan at a time.  Calls on one stream are ordered by the stream;
+ *   two streams (or two threads) that run the same plan at once would interleave on its work arrays -- give each its own plan.  (The Python host
+ *   keeps one plan per thread context, dtype and n and always launches on the current stream.)
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct mdsp_burg_plan_s* mdsp_burg_plan;
+int mdsp_burg_plan_create(mdsp_burg_plan* plan, int dtype, int64_t n, int64_t segments);
+int mdsp_burg_plan_destroy(mdsp_burg_plan plan);
+int mdsp_burg_plan_info(mdsp_burg_plan plan, int64_t* nsegments, int64_t* seglen, int64_t* tile, int64_t* workspace_bytes);
+int mdsp_burg_exec(mdsp_burg_plan plan, const void* x_dev, int64_t p, void* record_dev, void* stream);
+/* Pure host arithmetic, no device needed.  Any output pointer may be NULL. */
+int mdsp_burg_geometry_for(int dtype, int64_t n, int64_t segments, int64_t* nsegments, int64_t* seglen, int64_t* tile, int64_t* workspace_bytes);
+/* Host emulation of the whole recursion (no device): the same cut, tiles, arithmetic and order of additions (csrc/burg_op.h) on a host array. */
+int mdsp_burg_emulate_host(const void* x_host, int dtype, int64_t n, int64_t segments, int64_t p, void* record_host);
+
+/* ------------------------------------------------------------------------------------------------------
  * shiftsignal / shiftsignal! (src/util.jl:357-395): y[i] = x[i - s] where that exists, else 0, one line of l elements of 4, 8 or 16 bytes
  *   (moved as words: any element type).  in_place: out is the input.  Routes, chosen at plan creation and reported:
  *     MDSP_SHIFT_DISJOINT  out of place, or in place with 2 |s| >= l; one launch

@@ -28,7 +28,8 @@ export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, td
        mt_coherence, mt_coherence!, CrossPowerSpectra, Coherence, coherence, dpss, unwrap, unwrap!, sosfilt, sosfilt!,
        resp, resp_geometry, resp_emulate, impresp, stepresp,
        rms, rmsfft, meanfreq, finddelay, shiftsignal, shiftsignal!, alignsignals, alignsignals!, pow2db, amp2db, db2pow, db2amp,
-       jacobsen, quinn, quinn_geometry, quinn_pass_emulate
+       jacobsen, quinn, quinn_geometry, quinn_pass_emulate,
+       lpc, arburg, levinson, LPCBurg, LPCLevinson, burg_geometry, burg_emulate
 
 const lib = get(ENV, "MI355DSP_LIB", joinpath(@__DIR__, "..", "dsp.jl_amd", "libmi355dsp.so"))
 
@@ -799,6 +800,92 @@ end
 quinn(x::AbstractVector{T}, f0::Real, Fs::Real; kwargs...) where {T<:Number} = quinn(upload(convert(Vector{fftintype(T)}, x)), f0, Fs; kwargs...)
 quinn(x::AbstractVector; kwargs...) = quinn(x, jacobsen(x, 1.0), 1.0; kwargs...)              # :153
 quinn(x::AbstractVector, Fs::Real; kwargs...) = quinn(x, jacobsen(x, Fs), Fs; kwargs...)      # :155
+
+# ---------------------------------------------------------------------------------------------- lpc.jl:28-159
+# arburg / lpc(x, p, LPCBurg()): Burg's lattice passes on the device (mdsp_burg_*: two work arrays that do not move, 2 p launches, one copy of the
+# record); levinson is host code on p + 1 numbers; lpc(x, p, LPCLevinson()) is the device xcorr followed by levinson.
+struct LPCBurg end
+struct LPCLevinson end
+
+function burg_geometry(::Type{T}, n::Integer; segments::Integer=0) where {T}
+    S, seglen, tile, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_burg_geometry_for, lib), Cint, (Cint, Int64, Int64, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), mdtype(T), n, segments, S, seglen, tile, ws))
+    (segments=Int(S[]), seglen=Int(seglen[]), tile=Int(tile[]), workspace_bytes=Int(ws[]))
+end
+# the record: a (p + 1), the reflection coefficients (p), prediction_err in the real part of the last element
+burg_split(rec::Vector{T}, p::Integer) where {T} = (rec[1:p+1], real(rec[2p+2]), rec[p+2:2p+1])
+# the host emulation of the device code
+function burg_emulate(x::Vector{T}, p::Integer; segments::Integer=0) where {T<:Union{Float32,Float64,ComplexF32,ComplexF64}}
+    rec = zeros(T, 2p + 2)
+    GC.@preserve x rec check(ccall((:mdsp_burg_emulate_host, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ptr{Cvoid}),
+                                   pointer(x), mdtype(T), length(x), segments, p, pointer(rec)))
+    burg_split(rec, p)
+end
+# Burg's recursion of order p on a device vector into a device record of 2p + 2 elements; returns the cut the plan ran with
+function burg_exec!(rec::DeviceArray{T}, x::DeviceArray{T,1}, p::Integer; segments::Integer=0) where {T<:Union{Float32,Float64,ComplexF32,ComplexF64}}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_burg_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Cint, Int64, Int64), h, mdtype(T), length(x), segments))
+    try
+        S, seglen, tile, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_burg_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], S, seglen, tile, ws))
+        check(ccall((:mdsp_burg_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}), h[], x.ptr, p, rec.ptr, C_NULL))
+        return (segments=Int(S[]), seglen=Int(seglen[]), tile=Int(tile[]), workspace_bytes=Int(ws[]))
+    finally
+        ccall((:mdsp_burg_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+end
+# arburg(x, p): (a with its leading 1, prediction error, reflection coefficients).  0 <= p <= N - 1 (DSP.jl divides zero by zero at p = N)
+function arburg(x::DeviceArray{T,1}, p::Integer; segments::Integer=0) where {T<:Union{Float32,Float64,ComplexF32,ComplexF64}}
+    0 <= p <= length(x) - 1 || throw(ArgumentError("arburg: the order must be in [0, N - 1] = [0, $(length(x) - 1)], got $p"))
+    rec = DeviceArray{T}((2p + 2,))
+    burg_exec!(rec, x, p; segments=segments)
+    burg_split(download(rec), p)
+end
+arburg(x::AbstractVector{T}, p::Integer; kwargs...) where {T<:Number} = arburg(upload(convert(Vector{fftintype(T)}, x)), p; kwargs...)
+
+# lpc(x, p[, LPCBurg()]): arburg without the leading 1.  Host vectors and device vectors alike.
+const BurgInput = Union{AbstractVector,DeviceArray{<:Any,1}}
+lpc(x::BurgInput, p::Integer, ::LPCBurg) = (res = arburg(x, p); (res[1][2:end], res[2]))
+lpc(x::BurgInput, p::Integer) = lpc(x, p, LPCBurg())
+
+# levinson(r, p): the order-p solution of the Hermitian Toeplitz system whose first column is r[1:p], by Levinson's recursion on the host in the
+# promoted floating type of r: (coefficients without the leading 1, error, reflection coefficients).  A device vector is read by copying p + 1 lags.
+function levinson(r::AbstractVector{<:Number}, p::Integer)
+    (p >= 1 && length(r) >= p + 1) || throw(ArgumentError("levinson: p >= 1 and length(R_xx) >= p + 1 are needed"))
+    W = float(eltype(r))                      # Int -> Float64, Complex{Int} -> ComplexF64, Float32 stays
+    lag = W[r[i] for i in 1:p+1]              # lag[j + 1] is lag j
+    coef, refl, old = zeros(W, p), zeros(W, p), zeros(W, p)
+    gain = -lag[2] / lag[1]
+    coef[1] = refl[1] = gain
+    err = real(lag[1]) * (1 - abs2(gain))
+    for order in 2:p
+        copyto!(old, coef)
+        acc = zero(W)                         # sum over j of lag_j coef_(order - j), no conjugate, in ascending j
+        for j in 1:order-1
+            acc = muladd(lag[j+1], old[order-j], acc)
+        end
+        gain = -(lag[order+1] + acc) / err
+        for j in 1:order-1
+            coef[j] = muladd(gain, conj(old[order-j]), old[j])
+        end
+        coef[order] = refl[order] = gain
+        err *= 1 - abs2(gain)
+    end
+    coef, err, refl
+end
+levinson(r::DeviceArray{T,1}, p::Integer) where {T} = levinson(download(r)[1:min(p + 1, length(r))], p)
+
+# lpc(x, p, LPCLevinson()): the biased autocorrelation through the device xcorr, its lags 0 .. p, then levinson on the host.  A device vector is
+# downloaded first (xcorr takes host vectors and uploads them itself).
+function lpc(x::AbstractVector, p::Integer, ::LPCLevinson)
+    n = length(x)
+    1 <= p <= n - 1 || throw(ArgumentError("lpc: the order of the Levinson method must be in [1, N - 1]"))
+    full = xcorr(x; scaling=:biased)
+    lags = full isa DeviceArray ? download(full) : Array(full)
+    coef, err, _ = levinson(lags[n:n+p], p)
+    coef, err
+end
+lpc(x::DeviceArray{T,1}, p::Integer, m::LPCLevinson) where {T} = lpc(download(x), p, m)
 
 function shift_geometry(l::Integer, s::Integer, elem_bytes::Integer, in_place::Bool; tile::Integer=0, route::Integer=SHIFT_AUTO)
     r, t, c, n, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
