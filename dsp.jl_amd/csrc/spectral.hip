@@ -1365,10 +1365,12 @@ int welch_launch_n(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st) {
     if constexpr (!CPLX && N >= 256) {
         if (half_ok) {
             if constexpr (N == 4096 && sizeof(R) == 4) {
-                // The headline shape has four kernels, selectable with MDSP_WELCH_VARIANT when the plan is made:
+                // The headline shape has five kernels, selectable with MDSP_WELCH_VARIANT when the plan is made:
+                //   45 csrc/welch_w64e_asm.s: variant 44 with counted load waits (no full wait at the top of a unit).  The same arithmetic and the
+                //      same bits as 44; 1.21 against 1.28 ms (profiles/welch_w64e_ab.json).  The default where 44 was.
                 //   44 csrc/welch_w64d_asm.s: hand-allocated, one wavefront per transform, the half-frame two units share carried in registers, folded
-                //      twiddles.  It reduces into pl->reduced itself.  The default where the stream is long enough to give every wave of the chip a
-                //      unit and the schedule is one run per slot (MDSP_RUNS_PER_SLOT); 30 is the default otherwise.
+                //      twiddles.  It reduces into pl->reduced itself.  These kernels are the default where the stream is long enough to give every wave
+                //      of the chip a unit and the schedule is one run per slot (MDSP_RUNS_PER_SLOT); 30 is the default otherwise.
                 //   43 csrc/welch_w64c_asm.s: the same kernel before the twiddles were folded (13 % more vector instructions; 1.356 against 1.275 ms,
                 //      profiles/r07_welch_w64d_ab.json).  The tests compare 44 against it.
                 //   30 welch_half3_kernel: the HIP kernel for every other stream length and schedule (1.17 against 1.00 ms for 43 on an all-zero
@@ -1378,9 +1380,10 @@ int welch_launch_n(mdsp_welch_plan_s* pl, SpecArgs& a, hipStream_t st) {
                 if (pl->variant == 18) rc = welch_run_half<R, N, 16, 1, 1, 5, 1>(pl, a, st, &nslices);
                 else {
                     const bool long_enough = a.K / 2 >= (int64_t)device_cu_count() * 8 && tunables().runs_per_slot == 1;
-                    if (pl->variant == 43 || pl->variant == 44 || (pl->variant != 30 && long_enough)) {
+                    const bool forced = pl->variant == 43 || pl->variant == 44 || pl->variant == 45;
+                    if (forced || (pl->variant != 30 && long_enough)) {
                         bool handled = false;
-                        rc = w64::welch_run_w64asm(pl, a, st, &handled, pl->variant == 43 ? 43 : 44);
+                        rc = w64::welch_run_w64asm(pl, a, st, &handled, forced ? pl->variant : 45);
                         if (rc == MDSP_OK && handled) goto reduced_done;
                         if (rc != MDSP_OK) return rc;
                     }

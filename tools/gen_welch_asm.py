@@ -98,6 +98,8 @@ def render(ins, pmap):
         return f"{op} {R(ins.d)}, " + ", ".join(R(x) for x in ins.s) + modtext(ins.mods, len(ins.s))
     if op == "v_fma_f32":
         return f"v_fma_f32 {R(ins.d)}, {R(ins.s[0])}, {R(ins.s[1])}, {R(ins.s[2])}"
+    if op == "v_mul_f32":        # (gen_welch_asm_c.py's compact banks; verify_waits names such an instruction through this function)
+        return f"v_mul_f32_e32 {R(ins.d)}, {R(ins.s[0])}, {R(ins.s[1])}"
     if op == "ds_read_b64":
         return f"ds_read_b64 {R(ins.d)}, {R(ins.s[0])} offset:{ins.imm}"
     if op == "ds_write_b64":

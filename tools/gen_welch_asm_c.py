@@ -52,6 +52,8 @@ class GenC(W.Gen):
 
     NAME = NAME
     SCRIPT = "tools/gen_welch_asm_c.py"
+    TOP_WAIT = True      # every unit body starts with s_waitcnt vmcnt(0) (gen_welch_asm_e.py counts its waits instead: the bodies come without it)
+    LOAD_POLICY = ""     # cache policy suffix of the sample loads
     LDS_BYTES = LDS_BYTES
     WIN_OFF = WIN_OFF
     XB_OFF = XB_OFF
@@ -274,6 +276,8 @@ class EmuC(W.Emu):
 
 
 def build(G=GenC):
+    if hasattr(G, "build_pair"):
+        return G.build_pair()
     gA, gB = G(0), G(1)
     return gA, gB, gA.build_unit(), gB.build_unit(), G(0).build_first_loads()
 
@@ -325,7 +329,7 @@ def check(G=GenC):
     for i in bodyA:
         kinds[i.op] = kinds.get(i.op, 0) + 1
     nins = sum(v for k, v in kinds.items() if k != "comment")
-    nbad = W.verify_waits(loads + bodyA + bodyB + bodyA + bodyB)
+    nbad = W.verify_waits(loads + ([] if G.TOP_WAIT else [Ins("s_waitcnt_vm", imm=0)]) + bodyA + bodyB + bodyA + bodyB)
     print(f"emulated {nunits} units (A B A B A): relerr {err:.3e}, worst bin / max {worst:.3e}; {nins} instructions per unit ({valu_count(bodyA)} / {valu_count(bodyB)} vector ALU), "
           f"peak live pairs {gA.maxlive} / {gB.maxlive} of "
           f"{gA.NPOOL}, scheduler stall slots {gA.stalls} / {gB.stalls}, {gA.loads_in_body} / {gB.loads_in_body} of 64 loads inside the body, wait check: {nbad} problems")
@@ -416,9 +420,14 @@ def kernel_text(G=GenC):
     A("\ts_mov_b32 s30, 0x4000")
     A("\ts_mov_b32 s31, 0x00020000")
     A(f"\ts_mov_b32 s91, {FLUSH}                        ; units until the next flush")
+    def text_of(ins):
+        return render(ins, {}) + (G.LOAD_POLICY if ins.op == "buffer_load_dword" else "")
+
     for ins in loads:
         if W.keep(ins):
-            A("\t" + render(ins, {}))
+            A("\t" + text_of(ins))
+    if not G.TOP_WAIT:
+        A("\ts_waitcnt vmcnt(0)                            ; the first unit's samples: the bodies count their waits from an empty queue on")
 
     def flush():
         for kt in range(64):
@@ -431,17 +440,20 @@ def kernel_text(G=GenC):
         for s in range(64):
             A(f"\tv_mov_b32_e32 v{G.ACC0 + s}, 0")
         A(f"\ts_mov_b32 s91, {FLUSH}")
+        if not G.TOP_WAIT:
+            A("\ts_waitcnt vmcnt(0)                            ; the row stores never sit in the queue the counted waits of the bodies assume")
 
     for tag, other, body in (("A", "B", bodyA), ("B", "A", bodyB)):
         A(f".Lunit{tag}:")
-        A("\ts_waitcnt vmcnt(0)")
+        if G.TOP_WAIT:
+            A("\ts_waitcnt vmcnt(0)")
         A("\ts_add_u32 s24, s24, 0x4000                    ; the loads inside the body fetch the NEXT unit ...")
         A("\ts_addc_u32 s25, s25, 0")
         A("\ts_cmp_eq_u32 s87, 1")
         A("\ts_cselect_b32 s26, 0, 0x6000                  ; ... which does not exist behind this wave's last one: an empty descriptor returns zeros")
-        for ins in body[1:]:
+        for ins in (body[1:] if G.TOP_WAIT else body):
             if W.keep(ins):
-                A("\t" + render(ins, {}))
+                A("\t" + text_of(ins))
         A("\ts_sub_u32 s87, s87, 1")
         A("\ts_cmp_eq_u32 s87, 0")
         A(f"\ts_cbranch_scc1 .Lflush{tag}")
