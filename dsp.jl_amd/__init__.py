@@ -29,6 +29,7 @@ from .periodograms import (Periodogram, Periodogram2, Spectrogram, WelchConfig, 
 from .unwrap import unwrap, unwrap_, unwrap_geometry, UnwrapPlan  # noqa: F401
 from .response import freqresp, phaseresp, grpdelay, impresp, stepresp, RespPlan, resp_geometry  # noqa: F401
 from .estimation import jacobsen, quinn, QuinnPlan, quinn_geometry  # noqa: F401
+from .estimation import esprit, esprit_from_gram, hankel_gram, GramPlan, hankel_gram_geometry, ESPRIT_MAX_M  # noqa: F401
 from .lpc import LPCBurg, LPCLevinson, arburg, lpc, levinson, BurgPlan, burg_geometry  # noqa: F401
 from .comm import Comm  # noqa: F401
 from .channels import (channel_shard, welch_channel_mean, frame_shard, frame_span, welch_time_split,  # noqa: F401

@@ -172,6 +172,12 @@ PROTOTYPES = {
     "mdsp_burg_exec": (ci, [vp, vp, i64, vp, vp]),
     "mdsp_burg_geometry_for": (ci, [ci, i64, i64, pi64, pi64, pi64, pi64]),
     "mdsp_burg_emulate_host": (ci, [vp, ci, i64, i64, i64, vp]),
+    "mdsp_hankel_gram_plan_create": (ci, [pvp, ci, i64, i64, i64]),
+    "mdsp_hankel_gram_plan_destroy": (ci, [vp]),
+    "mdsp_hankel_gram_plan_info": (ci, [vp, pi64, pi64, pi64, pi64, pi64]),
+    "mdsp_hankel_gram_exec": (ci, [vp, vp, vp, i64, vp]),
+    "mdsp_hankel_gram_geometry_for": (ci, [ci, i64, i64, i64, pi64, pi64, pi64, pi64, pi64]),
+    "mdsp_hankel_gram_emulate_host": (ci, [vp, ci, i64, i64, i64, vp, i64]),
     "mdsp_shift_plan_create": (ci, [pvp, i64, i64, i64, ci, i64, ci]),
     "mdsp_shift_plan_destroy": (ci, [vp]),
     "mdsp_shift_plan_info": (ci, [vp, pint, pi64, pi64, pi64, pi64]),

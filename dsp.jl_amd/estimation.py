@@ -1,5 +1,6 @@
-"""DSP.jl ``src/estimation.jl`` on the device: ``jacobsen`` and ``quinn`` (``mdsp_est_*``, ``mdsp_quinn_*``).  ``esprit`` is out of scope
-(a dense SVD).
+"""DSP.jl ``src/estimation.jl`` on the device: ``jacobsen`` and ``quinn`` (``mdsp_est_*``, ``mdsp_quinn_*``) and ``esprit`` (the Gram matrix
+of its Hankel matrix by ``mdsp_hankel_gram_*``, the ``M x M`` eigenproblem on the host).  ``esprit`` refuses ``p >= M``, ``2 M - 1 > N`` and
+``M > ESPRIT_MAX_M``.
 
 Vectors only; numpy or a device tensor in, Python numbers out (every call ends in one small copy to the host).  No CPU fallback.
 """
@@ -163,3 +164,118 @@ def quinn(x, *args, tol=1e-6, maxiters=20):
     plan = _plancache.plans.get(("quinn", _plancache.ctx_key(), W.str, n), lambda: QuinnPlan(W, n))
     est, reached, _ = plan.estimate(_dev.ptr(xd), f0, fs, tol, int(maxiters))
     return est, reached
+
+
+ESPRIT_MAX_M = 1024      # the largest correlation matrix esprit takes: a cap on the host eigenproblem and on the 16 MiB of R, not on the kernels
+
+
+class GramPlan:
+    """``mdsp_hankel_gram_plan`` for vectors of ``n`` samples of ``dtype`` and ``M`` rows: ``segments``, ``seglen``, ``tile``, ``lag_group``, ``workspace_bytes``.
+    ``segments`` = 0 lets the library cut the body range; a positive value forces the cut (tests, tools/esprit_bench.py)."""
+
+    def __init__(self, dtype, n, M, segments=0):
+        self._h = C.c_void_p()
+        self.dtype, self.n, self.M = np.dtype(dtype), int(n), int(M)
+        self.out_dtype = np.dtype(np.complex128 if self.dtype.kind == "c" else np.float64)
+        _lib.check(_lib.lib().mdsp_hankel_gram_plan_create(C.byref(self._h), _dev.md_dtype(self.dtype), self.n, self.M, int(segments)))
+        S, seglen, tile, group, ws = (C.c_int64() for _ in range(5))
+        _lib.check(_lib.lib().mdsp_hankel_gram_plan_info(self._h, C.byref(S), C.byref(seglen), C.byref(tile), C.byref(group), C.byref(ws)))
+        self.segments, self.seglen, self.tile, self.lag_group, self.workspace_bytes = S.value, seglen.value, tile.value, group.value, ws.value
+
+    def exec(self, x_ptr: int, r_ptr: int, ldr: int | None = None, stream: int | None = None):
+        """``R`` (``M x M``, column-major, leading dimension ``ldr`` -- ``M`` where none is given --, elements of ``out_dtype``) goes to ``r_ptr``."""
+        _lib.check(_lib.lib().mdsp_hankel_gram_exec(self._h, x_ptr, r_ptr, self.M if ldr is None else int(ldr), _dev.stream_ptr() if stream is None else stream))
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().mdsp_hankel_gram_plan_destroy(self._h)
+        except Exception:
+            pass
+
+
+def hankel_gram_geometry(dtype, n: int, M: int, segments: int = 0):
+    """(segments, seglen, tile, lag_group, workspace_bytes) a plan for these arguments has: host arithmetic of the library, no device needed."""
+    S, seglen, tile, group, ws = (C.c_int64() for _ in range(5))
+    _lib.check(_lib.lib().mdsp_hankel_gram_geometry_for(_dev.md_dtype(dtype), int(n), int(M), int(segments), C.byref(S), C.byref(seglen), C.byref(tile),
+                                                        C.byref(group), C.byref(ws)))
+    return S.value, seglen.value, tile.value, group.value, ws.value
+
+
+def _integer(v, what, name):
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+        raise TypeError(f"{what}: {name} must be an integer, got {type(v).__name__}")
+    return int(v)
+
+
+def _signal(x, what):
+    """(x, working dtype) of an array of numbers, before any device work."""
+    if not hasattr(x, "shape"):
+        x = np.asarray(x)
+    dt = _dev.np_dtype_of(x)
+    if dt.kind not in "fciub":
+        raise TypeError(f"{what}: an array of numbers expected")
+    if dt == np.dtype(np.float16):
+        raise UnsupportedError(f"{what}: element type {dt} is not accelerated")
+    return x, _work_dtype(dt, what)
+
+
+def hankel_gram(x, M):
+    """``R = X X^H`` of the Hankel matrix ``X[i, k] = x[i + k]`` with ``M`` rows and ``N - M + 1`` columns (estimation.jl:70) of a vector ``x``: ``M x M``, Float64
+    for a real signal and ComplexF64 for a complex one, exactly Hermitian.  Numpy in gives numpy out, a device tensor in gives a device tensor out (a
+    column-major view).  ``1 <= M`` and ``2 M - 1 <= N``."""
+    x, W = _signal(x, "hankel_gram")
+    if len(x.shape) != 1:
+        raise TypeError("hankel_gram: a vector of numbers expected")
+    M, n = _integer(M, "hankel_gram", "M"), int(x.shape[0])
+    if M < 1:
+        raise ArgumentError(f"hankel_gram: M >= 1 is needed (got {M})")
+    if 2 * M - 1 > n:
+        raise UnsupportedError(f"hankel_gram: 2 M - 1 <= N is needed (M = {M}, N = {n})")
+    _lib.require_device()
+    xd = _dev.as_device(x, W).contiguous()
+    plan = _plancache.plans.get(("hankel_gram", _plancache.ctx_key(), W.str, n, M), lambda: GramPlan(W, n, M))
+    r = _dev.torch.empty((M, M), dtype=_dev.torch_dtype(plan.out_dtype), device=xd.device)
+    plan.exec(_dev.ptr(xd), _dev.ptr(r))
+    r = r.t()                                                                          # the library wrote columns
+    return r if _dev.is_device_array(x) else r.cpu().numpy()
+
+
+def esprit_from_gram(R, p: int, fs: float = 1.0) -> np.ndarray:
+    """The host finish of ``esprit`` (estimation.jl:71-74) from the Gram matrix: the ``p`` eigenvectors of the largest eigenvalues of ``R`` span what the first
+    ``p`` left singular vectors of the Hankel matrix span, and the eigenvalues of ``U[:-1] \\ U[1:]`` do not depend on the basis.  Float64 vector of length ``p``."""
+    R = np.asarray(R)
+    if not np.isfinite(R).all():
+        raise ArgumentError("esprit: the signal holds Infs or NaNs")                  # the reference's svd refuses them before LAPACK
+    _, V = np.linalg.eigh(R)                                                           # eigenvalues ascending
+    U = V[:, ::-1][:, :p]
+    psi = np.linalg.lstsq(U[:-1], U[1:], rcond=None)[0]
+    return np.asarray(np.angle(np.linalg.eigvals(psi)) * (fs / (2 * np.pi)), dtype=np.float64)
+
+
+def esprit(x, M, p, Fs=1.0) -> np.ndarray:
+    """``esprit(x, M, p, Fs=1.0)`` (estimation.jl:67-75): the frequencies of ``p`` cisoids in ``x`` from the signal subspace of the ``M x (N - M + 1)`` Hankel matrix
+    of ``x``.  The reference takes the subspace from an SVD of that matrix; here the device forms its ``M x M`` Gram matrix in Float64 (``hankel_gram``), and the
+    host takes ``eigh`` of it, the ``p`` leading eigenvectors, ``lstsq`` and ``eigvals``.  Squaring the singular values loses a component whose singular value is
+    below about ``sqrt(eps)`` of the largest.  The order of the frequencies is unspecified, as in the reference.
+
+    ``x`` has at most one non-singleton dimension.  ``p < 1`` or ``M > N``: ``ArgumentError`` (a ``BoundsError`` in the reference).  ``p >= M`` (the reference solves an
+    under-determined system), ``2 M - 1 > N`` and ``M > ESPRIT_MAX_M``: ``UnsupportedError``.  Infs and NaNs: ``ArgumentError``."""
+    x, W = _signal(x, "esprit")
+    if sum(int(s) != 1 for s in x.shape) > 1:
+        raise ArgumentError("`x` must be a 1D signal")
+    M, p, fs = _integer(M, "esprit", "M"), _integer(p, "esprit", "p"), _fs(Fs, "esprit")
+    n = 1
+    for s in x.shape:
+        n *= int(s)
+    if p < 1 or M < 1 or M > n:
+        raise ArgumentError(f"esprit: p >= 1 and 1 <= M <= N are needed (M = {M}, p = {p}, N = {n})")
+    if p >= M:
+        raise UnsupportedError(f"esprit: p < M is needed (M = {M}, p = {p})")
+    if 2 * M - 1 > n:
+        raise UnsupportedError(f"esprit: 2 M - 1 <= N is needed (M = {M}, N = {n})")
+    if M > ESPRIT_MAX_M:
+        raise UnsupportedError(f"esprit: M <= {ESPRIT_MAX_M} is needed (got {M})")
+    _lib.require_device()
+    R = hankel_gram(_dev.as_device(x, W).reshape(-1), M)
+    return esprit_from_gram(R.cpu().numpy(), p, fs)

@@ -564,6 +564,35 @@ int mdsp_burg_geometry_for(int dtype, int64_t n, int64_t segments, int64_t* nseg
 int mdsp_burg_emulate_host(const void* x_host, int dtype, int64_t n, int64_t segments, int64_t p, void* record_host);
 
 /* ------------------------------------------------------------------------------------------------------
+ * The Gram matrix of esprit's Hankel matrix (src/estimation.jl:69-71): for one vector of n samples of dtype F, X[i, k] = x[i + k] with M rows and
+ *   L = n - M + 1 columns, R = X X^H (csrc/gram.hip, csrc/gram_op.h).  The first p left singular vectors of X span the dominant
+ *   p-dimensional eigenspace of R, which is all esprit uses of the SVD; the hosts finish with an M x M Hermitian eigenproblem.
+ *   R: M x M, column-major with leading dimension ldr >= M, Float64 for a real F and ComplexF64 for a complex one; aligned to 8 bytes.  Exactly
+ *   Hermitian (the upper triangle is stored as the conjugate of the lower), the diagonal's imaginary part +0.0.  Rows M .. ldr - 1 are not touched.
+ *   R[j + d, j] is a window sum of x[k + d] conj(x[k]) over L values of k: the body k = M - 1 .. L - 1 that all windows of a diagonal share (one
+ *   pass over the signal for all M lags: a partial per (segment, lag), stored, then summed in segment order) plus a head and a tail of at most
+ *   M - 1 products each (one lane per diagonal, two running sums); never a difference of running totals.  Products and sums in Float64.  Two
+ *   launches on one stream.  No atomics, nothing waits: R depends on (x, M, the cut) only and equals mdsp_hankel_gram_emulate_host bit for bit.
+ *   x is never written.
+ *   segments: 0 = automatic, > 0 forced: the cut of the body range into ceil((n - 2 M + 2) / segments) samples each.  tile: samples a workgroup
+ *   stages at a time; lag_group: lags a lane accumulates at a time.  workspace_bytes: nsegments x M partials of 8 (real) or 16 bytes.
+ *   Checks, before any launch: a bad dtype, n < 0, M < 1, segments < 0, ldr < M, NULL or misaligned buffers: MDSP_ERR_ARGUMENT.  2 M - 1 > n (the
+ *   windows would share no body; the transposed Hankel matrix has the same row space question turned round) or M > 2^20: MDSP_ERR_UNSUPPORTED.
+ *   A plan touches the device at its first exec (allocations: not inside a stream capture); the partials belong to the PLAN: one exec at a time.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct mdsp_hankel_gram_plan_s* mdsp_hankel_gram_plan;
+int mdsp_hankel_gram_plan_create(mdsp_hankel_gram_plan* plan, int dtype, int64_t n, int64_t M, int64_t segments);
+int mdsp_hankel_gram_plan_destroy(mdsp_hankel_gram_plan plan);
+int mdsp_hankel_gram_plan_info(mdsp_hankel_gram_plan plan, int64_t* nsegments, int64_t* seglen, int64_t* tile, int64_t* lag_group,
+                               int64_t* workspace_bytes);
+int mdsp_hankel_gram_exec(mdsp_hankel_gram_plan plan, const void* x_dev, void* r_dev, int64_t ldr, void* stream);
+/* Pure host arithmetic, no device needed.  Any output pointer may be NULL. */
+int mdsp_hankel_gram_geometry_for(int dtype, int64_t n, int64_t M, int64_t segments, int64_t* nsegments, int64_t* seglen, int64_t* tile,
+                                  int64_t* lag_group, int64_t* workspace_bytes);
+/* Host emulation (no device): the same cut, tiles, arithmetic and order of additions (csrc/gram_op.h) on a host array. */
+int mdsp_hankel_gram_emulate_host(const void* x_host, int dtype, int64_t n, int64_t M, int64_t segments, void* r_host, int64_t ldr);
+
+/* ------------------------------------------------------------------------------------------------------
  * shiftsignal / shiftsignal! (src/util.jl:357-395): y[i] = x[i - s] where that exists, else 0, one line of l elements of 4, 8 or 16 bytes
  *   (moved as words: any element type).  in_place: out is the input.  Routes, chosen at plan creation and reported:
  *     MDSP_SHIFT_DISJOINT  out of place, or in place with 2 |s| >= l; one launch

@@ -17,7 +17,7 @@
 # calling thread); the multi-GPU part is `Comm` (RCCL behind the C ABI).  Reference locations are DSP.jl v0.8.5 `src/`.
 module MI355DSP
 
-using LinearAlgebra: SymTridiagonal, eigen
+using LinearAlgebra: Hermitian, SymTridiagonal, eigen
 
 export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, tdfilt!, conv, conv!, xcorr, hilbert,
        Periodogram, Periodogram2, Spectrogram, power, freq, fftshift, arraysplit, periodogram, WelchConfig, welch_pgram, welch_pgram!,
@@ -29,7 +29,8 @@ export DeviceArray, upload, download, filt, filt!, fftfilt, fftfilt!, tdfilt, td
        resp, resp_geometry, resp_emulate, impresp, stepresp,
        rms, rmsfft, meanfreq, finddelay, shiftsignal, shiftsignal!, alignsignals, alignsignals!, pow2db, amp2db, db2pow, db2amp,
        jacobsen, quinn, quinn_geometry, quinn_pass_emulate,
-       lpc, arburg, levinson, LPCBurg, LPCLevinson, burg_geometry, burg_emulate
+       lpc, arburg, levinson, LPCBurg, LPCLevinson, burg_geometry, burg_emulate,
+       esprit, esprit_from_gram, hankel_gram, hankel_gram_geometry, hankel_gram_emulate
 
 const lib = get(ENV, "MI355DSP_LIB", joinpath(@__DIR__, "..", "dsp.jl_amd", "libmi355dsp.so"))
 
@@ -886,6 +887,64 @@ function lpc(x::AbstractVector, p::Integer, ::LPCLevinson)
     coef, err
 end
 lpc(x::DeviceArray{T,1}, p::Integer, m::LPCLevinson) where {T} = lpc(download(x), p, m)
+
+# ---------------------------------------------------------------------------------------------- estimation.jl:67-75
+# esprit: the Gram matrix R = X X' of the M x (N - M + 1) Hankel matrix on the device (mdsp_hankel_gram_*: two launches, Float64 sums stored and added
+# in a fixed order), then eigen(Hermitian(R)), the p leading eigenvectors, \ and eigen on the host.  The span of those eigenvectors is the span of the
+# first p left singular vectors the reference takes from svd(X).
+const ESPRIT_MAX_M = 1024      # a cap on the host eigenproblem and on the 16 MiB of R, not on the kernels
+gramtype(::Type{T}) where {T<:Real} = Float64
+gramtype(::Type{T}) where {T<:Complex} = ComplexF64
+
+function hankel_gram_geometry(::Type{T}, n::Integer, M::Integer; segments::Integer=0) where {T}
+    S, seglen, tile, group, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:mdsp_hankel_gram_geometry_for, lib), Cint, (Cint, Int64, Int64, Int64, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}),
+                mdtype(T), n, M, segments, S, seglen, tile, group, ws))
+    (segments=Int(S[]), seglen=Int(seglen[]), tile=Int(tile[]), lag_group=Int(group[]), workspace_bytes=Int(ws[]))
+end
+# the host emulation of the device code
+function hankel_gram_emulate(x::Vector{T}, M::Integer; segments::Integer=0) where {T<:Union{Float32,Float64,ComplexF32,ComplexF64}}
+    R = zeros(gramtype(T), M, M)
+    GC.@preserve x R check(ccall((:mdsp_hankel_gram_emulate_host, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Int64, Int64, Ptr{Cvoid}, Int64),
+                                 pointer(x), mdtype(T), length(x), M, segments, pointer(R), M))
+    R
+end
+# R of a device vector as a host matrix (column-major, as the library writes it)
+function hankel_gram(x::DeviceArray{T,1}, M::Integer; segments::Integer=0) where {T<:Union{Float32,Float64,ComplexF32,ComplexF64}}
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:mdsp_hankel_gram_plan_create, lib), Cint, (Ref{Ptr{Cvoid}}, Cint, Int64, Int64, Int64), h, mdtype(T), length(x), M, segments))
+    try
+        S, seglen, tile, group, ws = Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
+        check(ccall((:mdsp_hankel_gram_plan_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}, Ref{Int64}), h[], S, seglen, tile, group, ws))
+        R = DeviceArray{gramtype(T)}((M, M))
+        check(ccall((:mdsp_hankel_gram_exec, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}), h[], x.ptr, R.ptr, M, C_NULL))
+        return download(R)
+    finally
+        ccall((:mdsp_hankel_gram_plan_destroy, lib), Cint, (Ptr{Cvoid},), h[])
+    end
+end
+hankel_gram(x::AbstractVector{T}, M::Integer; kwargs...) where {T<:Number} = hankel_gram(upload(convert(Vector{fftintype(T)}, x)), M; kwargs...)
+
+# the host finish (:71-74) from the Gram matrix
+function esprit_from_gram(R::AbstractMatrix, p::Integer, Fs::Real=1.0)
+    all(isfinite, R) || throw(ArgumentError("esprit: the signal holds Infs or NaNs"))          # the reference's svd refuses them
+    V = eigen(Hermitian(Matrix(R))).vectors                                                     # eigenvalues ascending
+    U = V[:, end:-1:end-p+1]
+    D = eigen(U[1:end-1, :] \ U[2:end, :]).values
+    Float64.(angle.(D) .* (Fs / 2π))
+end
+
+# esprit(x, M, p, Fs=1.0).  p < 1 or M > N: ArgumentError (a BoundsError in DSP.jl); p >= M, 2M - 1 > N, M > ESPRIT_MAX_M: UnsupportedError
+function esprit(x::Union{AbstractArray{<:Number},DeviceArray}, M::Integer, p::Integer, Fs::Real=1.0)
+    count(!isone, size(x)) <= 1 || throw(ArgumentError("`x` must be a 1D signal"))              # :68
+    N = length(x)
+    (p >= 1 && 1 <= M <= N) || throw(ArgumentError("esprit: p >= 1 and 1 <= M <= N are needed (M = $M, p = $p, N = $N)"))
+    p < M || throw(UnsupportedError("esprit: p < M is needed (M = $M, p = $p)"))
+    2M - 1 <= N || throw(UnsupportedError("esprit: 2 M - 1 <= N is needed (M = $M, N = $N)"))
+    M <= ESPRIT_MAX_M || throw(UnsupportedError("esprit: M <= $ESPRIT_MAX_M is needed (got $M)"))
+    v = x isa DeviceArray ? (ndims(x) == 1 ? x : upload(vec(download(x)))) : vec(collect(x))
+    esprit_from_gram(hankel_gram(v, M), p, Fs)
+end
 
 function shift_geometry(l::Integer, s::Integer, elem_bytes::Integer, in_place::Bool; tile::Integer=0, route::Integer=SHIFT_AUTO)
     r, t, c, n, ws = Ref{Cint}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0), Ref{Int64}(0)
