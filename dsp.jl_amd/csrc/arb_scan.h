@@ -4,7 +4,7 @@
 //
 // which the reference runs serially, one output at a time, and whose state decides every index on this path (which
 // input samples and which filter phase feed output k, how many outputs a call produces, the state it leaves behind).
-// The serial host loop (arb_trajectory in fir.hip) costs about 1 ns per output -- two orders of magnitude more than the
+// The serial host loop (arb_trajectory in fir_arb.hip) costs about 1 ns per output -- two orders of magnitude more than the
 // filtering kernel -- so long streams evaluate the SAME recurrence in parallel on the device, bit for bit:
 //
 //  * Grid.  After one update acc is a multiple of g = ulp(delta): fl(acc + delta) >= delta is a multiple of its own
@@ -30,7 +30,7 @@
 //    E, which certifies it block by block if it was right; a run rejected twice falls back to the serial host loop,
 //    so the result is exact either way.
 //
-// Everything here is plain integer code shared by the device kernels (fir.hip) and a host driver used by the CPU tests.
+// Everything here is plain integer code shared by the device kernels (fir_arb.hip) and a host driver used by the CPU tests.
 #pragma once
 
 #include <cfloat>
@@ -47,7 +47,7 @@ namespace mdsp {
 namespace arbscan {
 
 constexpr int BLK = 32;        // updates per scan block
-constexpr int ANCH = 16;       // outputs per anchor (ARB_BLK in fir.hip): two anchors per block, the second from finalize's own replay
+constexpr int ANCH = 16;       // outputs per anchor (ARB_BLK in fir_arb.hip): two anchors per block, the second from finalize's own replay
 constexpr int RMAX = 16;       // table entries: residues of E modulo 2^(J+1), J <= 3
 constexpr int FAN = 64;        // tables composed per thread in one scan level
 

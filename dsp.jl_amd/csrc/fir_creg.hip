@@ -12,19 +12,15 @@
 #include "fir_creg.h"
 
 #include "devio.h"
-#include "fft_lds.h"
+#include "fir_op.h"
 
 using namespace mdsp;
+using mdsp::firop::to_acc;
 using mdsp::fft::cx;
 
 namespace {
 
 template <typename R> using v2 = R __attribute__((ext_vector_type(2)));
-
-template <typename R> __device__ __forceinline__ R to_z(float v, R*) { return (R)v; }
-template <typename R> __device__ __forceinline__ R to_z(double v, R*) { return (R)v; }
-template <typename R> __device__ __forceinline__ cx<R> to_z(cx<float> v, cx<R>*) { return {(R)v.x, (R)v.y}; }
-template <typename R> __device__ __forceinline__ cx<R> to_z(cx<double> v, cx<R>*) { return {(R)v.x, (R)v.y}; }
 
 // acc += h x, h = (re, im)
 template <typename R> __device__ __forceinline__ void cfma(v2<R>& acc, v2<R> h, R x) { acc = __builtin_elementwise_fma(v2<R>{x, x}, h, acc); }
@@ -99,14 +95,14 @@ __global__ __launch_bounds__(LB) void polyphase_creg_kernel(FirRegArgs a) {
                 for (int u = 0; u < 4; ++u) v[u] = io::Ld<XS>::load(rs, (k2 + u * step) * (int)sizeof(XS));
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
-                    if (k2 + u * step < nz) zs[k2 + u * step] = to_z(v[u], (Z*)nullptr);
+                    if (k2 + u * step < nz) zs[k2 + u * step] = to_acc(v[u], (Z*)nullptr);
             }
         } else {           // the first tile(s) straddle the history
             for (int k2 = threadIdx.x; k2 < nz; k2 += blockDim.x) {
                 const int64_t zi = z0 + k2;
                 Z v{};
-                if (zi < a.hl) v = to_z(hc[zi], (Z*)nullptr);
-                else if (zi - a.hl < a.xlen) v = to_z(xc[zi - a.hl], (Z*)nullptr);
+                if (zi < a.hl) v = to_acc(hc[zi], (Z*)nullptr);
+                else if (zi - a.hl < a.xlen) v = to_acc(xc[zi - a.hl], (Z*)nullptr);
                 zs[k2] = v;
             }
         }

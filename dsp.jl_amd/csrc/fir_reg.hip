@@ -11,22 +11,14 @@
 #include "fir_reg.h"
 
 #include "devio.h"
-#include "fft_lds.h"
+#include "fir_op.h"
 
 using namespace mdsp;
+using namespace mdsp::firop;
 using mdsp::fft::cx;
 
 namespace {
 
-template <typename R> __device__ __forceinline__ R to_acc(float v, R*) { return (R)v; }
-template <typename R> __device__ __forceinline__ R to_acc(double v, R*) { return (R)v; }
-template <typename R> __device__ __forceinline__ cx<R> to_acc(cx<float> v, cx<R>*) { return {(R)v.x, (R)v.y}; }
-template <typename R> __device__ __forceinline__ cx<R> to_acc(cx<double> v, cx<R>*) { return {(R)v.x, (R)v.y}; }
-template <typename R> __device__ __forceinline__ void fma_acc(R& acc, R h, R x) { acc = fma(x, h, acc); }
-template <typename R> __device__ __forceinline__ void fma_acc(cx<R>& acc, R h, cx<R> x) {
-    acc.x = fma(x.x, h, acc.x);
-    acc.y = fma(x.y, h, acc.y);
-}
 template <typename A> __device__ __forceinline__ A zero_acc() { return A{}; }
 
 // XS: storage type of x; A: accumulate / output type (R or cx<R>); R: tap type

@@ -1,5 +1,5 @@
 """Case table of tests/test_gpu_arb_paths.py and tests/test_arb_reference_cpu.py: arbitrary-rate FIRFilter shapes on the boundaries of the
-launch decisions of arbitrary_fir_kernel (csrc/fir.hip, arb_geometry), each with the geometry mdsp_arb_kernel_geometry must report.  The
+launch decisions of arbitrary_fir_kernel (csrc/fir_arb.hip, arb_geometry), each with the geometry mdsp_arb_kernel_geometry must report.  The
 geometry was read off the predicates (256 compute units):
 
     taps_in_lds  2 tp nphi sizeof(R) <= 32 KiB

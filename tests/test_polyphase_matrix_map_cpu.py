@@ -1,7 +1,7 @@
 """The algebra behind the matrix-core polyphase kernel, replayed in numpy on the host: rows of RB rounds, blocks of 16 output columns,
 H[k][j] = pfb[phase_j][k - delta_j], X[row][k] = z[row Mr + c_block + k], Y = X H -- with the geometry the library itself chooses
 (mdsp_fir_mm_geometry, no device needed) -- against the oracle's FIRFilter (stream_filt.jl:476-515 restated).  The GPU tests compare the
-kernel with the oracle; this one pins the index arithmetic the kernel implements (dsp.jl_amd/csrc/fir.hip, polyphase_mfma_kernel)."""
+kernel with the oracle; this one pins the index arithmetic the kernel implements (dsp.jl_amd/csrc/fir_mm.hip, polyphase_mfma_kernel)."""
 import ctypes as C
 from fractions import Fraction
 from math import gcd
@@ -113,7 +113,7 @@ def test_matrix_form_random_shapes():
 
 
 def test_padded_run_addressing_model():
-    """Round 3, padded runs (fir.hip, polyphase_mfma_kernel<..., RP = true>): a tile is staged as one run of 256-dword DMA granules with PAD dwords
+    """Round 3, padded runs (fir_mm.hip, polyphase_mfma_kernel<..., RP = true>): a tile is staged as one run of 256-dword DMA granules with PAD dwords
     behind every granule (dword d of the tile at d + PAD (d >> 8)); a lane reads its window positions through ONE of two base pointers -- the
     window's start, or PAD further on from the step at which the window crosses a granule boundary -- with immediate offsets 4 t DW.  Replayed
     here for random geometries: every read lands on the sample the plain run would have read, no read lands on a pad, the crossing step is the
