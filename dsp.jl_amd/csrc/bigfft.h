@@ -7,7 +7,7 @@
 namespace mdsp {
 namespace big {
 
-// nfft the engine plans: 7-smooth, above the single-workgroup kernels of spectral.hip, splitting into 2..4 factors of at most 512
+// nfft the engine plans: 7-smooth, above the single-workgroup kernels of welch.hip and stft.hip, splitting into 2..4 factors of at most 512
 bool size_ok(int dtype, int64_t nfft);
 
 struct Engine;

@@ -1,6 +1,6 @@
 // Multi-pass fused spectral engine: Welch sums, STFT / spectrogram / periodogram columns for transforms of 2^13 .. 2^30 points (bigfft.h).
 //
-// Reference loops being replaced (src/periodograms.jl) -- the same four as spectral.hip, at the sizes the reference's DEFAULT arguments ask for
+// Reference loops being replaced (src/periodograms.jl) -- the same four as welch.hip and stft.hip, at the sizes the reference's DEFAULT arguments ask for
 // (n = length(s) >> 3, nfft = nextfastfft(n): :560, :647, :828, :872):
 //   K4  ArraySplit getindex :57-69     buf[i] = s[offset+i] * window[i], zero tail up to nfft   -> the loads of pass 0
 //   F3  mul!(outbuf, plan, sig) :754, :888                                                       -> P passes of bigfft_pass.h, one launch each
@@ -31,7 +31,7 @@ namespace mdsp {
 // ols.hip: the row kernel of the long-filter convolution and the root table of its transforms
 int ols_rows(int dbl, void* work, int64_t rows, int hrows, const void* Hrows, const void* table, const void* rt0, const void* rt1, int rlogS, hipStream_t st);
 int ols_rows_table(int dbl, DevBuf& buf);
-// spectral.hip: |FFT_S|^2 of `nch` rows, K frames `hop` apart, summed into the row plan's Float64 accumulator
+// welch.hip: |FFT_S|^2 of `nch` rows, K frames `hop` apart, summed into the row plan's Float64 accumulator
 int welch_rows_accumulate(mdsp_welch_plan_s* pl, const void* work, int64_t K, int64_t hop, int64_t nch, hipStream_t st);
 namespace big {
 
@@ -47,7 +47,7 @@ struct Engine {
     int rowsR0 = 0;
     Pass inv0;
     DevBuf rowtab;                     // the S forward roots of the row transforms (ols.hip)
-    mdsp_welch_plan rowplan = nullptr; // Welch, rows form: the S-point complex plan whose single-workgroup kernel sums |Z|^2 over the rows (spectral.hip)
+    mdsp_welch_plan rowplan = nullptr; // Welch, rows form: the S-point complex plan whose single-workgroup kernel sums |Z|^2 over the rows (welch.hip)
     ~Engine() {
         if (rowplan) mdsp_welch_plan_destroy(rowplan);
     }
@@ -817,7 +817,7 @@ __global__ __launch_bounds__(256) void big_rows_to_natural_kernel(const double* 
 
 // Welch in the rows form: nfft = R0 x S.  The column pass reads the windowed frames (two real frames per transform) and leaves the twiddled columns in the
 // work buffer; the rows are then complex frames of S points, R0 channels of them, K transforms `nfft` elements apart, for the single-workgroup Welch
-// kernel (spectral.hip): two trips through HBM per transform instead of three, and no natural-order pass -- |Z|^2 is summed row-major and transposed once.
+// kernel (welch.hip): two trips through HBM per transform instead of three, and no natural-order pass -- |Z|^2 is summed row-major and transposed once.
 template <typename R, bool CPLX>
 int run_welch_rows(Engine* e, const void* s, int64_t K, int64_t hop, const double* win_dev, double* acc, bool fresh, hipStream_t st) {
     const int64_t N = e->nfft, S = N / e->rowsR0;
@@ -922,8 +922,8 @@ int ols(EngineHolder& h, int dtype, int64_t N, int R0, const void* x, int64_t nx
 
 bool size_ok(int dtype, int64_t nfft) {
     if (!tunables().bigfft) return false;
-    // above the single-workgroup kernels of spectral.hip (which keep precedence where they exist: power-of-two register forms to 8192 / 4096,
-    // mixed-radix LDS forms to 8192 / 8000 -- spectral.hip use_big)
+    // above the single-workgroup kernels of welch.hip and stft.hip (which keep precedence where they exist: power-of-two register forms to 8192 / 4096,
+    // mixed-radix LDS forms to 8192 / 8000 -- spectral.hip choose_spectral_route)
     (void)dtype;
     if (nfft <= 4096 || nfft >= ((int64_t)1 << 31) || !seven_smooth(nfft)) return false;
     int R[MAXP];

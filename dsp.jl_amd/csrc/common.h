@@ -129,7 +129,7 @@ struct Tunables {
     int ols_prio = 1;                   // MDSP_OLS_PRIO            : overlap-save kernel: bit 0 loads, bit 1 stores issued at raised wave priority (default 1:
                                         //                            1.799 -> 1.774 ms per 2^30 samples, profiles/r03l_tune_prio.json)
     int ols_variant = 0;                // MDSP_OLS_VARIANT         : kernel form of the PARTITIONED overlap-save plans only, 0-8 (ols.hip launch_upols_np)
-    int welch_variant = 0;              // MDSP_WELCH_VARIANT       : Welch kernel of the real Float32 nfft-4096 half-frame shape: 18, 30, 43, 44 or 45 (spectral.hip
+    int welch_variant = 0;              // MDSP_WELCH_VARIANT       : Welch kernel of the real Float32 nfft-4096 half-frame shape: 18, 30, 43, 44 or 45 (welch.hip
                                         //                            welch_launch_n); any other number: the default rule
     int rocfft_chunk_mib = 192;         // MDSP_ROCFFT_CHUNK_MIB    : intermediates per rocFFT-engine chunk
     int fir_lds_kib = 20;               // MDSP_FIR_LDS_KIB         : staging tile of the fast polyphase kernel
@@ -217,6 +217,6 @@ int plan_cache_get(const std::string& key, void** out, const std::function<int(v
 #define MDSP_ABLATED(a, bit) false
 #endif
 
-// spectral.hip: out[j] = (R)(sum over channels of psd[c][j]) (* scale, rounded once more) -- the local part of the cross-channel Welch mean (comm.hip)
+// welch.hip: out[j] = (R)(sum over channels of psd[c][j]) (* scale, rounded once more) -- the local part of the cross-channel Welch mean (comm.hip)
 int channel_sum_scaled(const void* psd_dev, int64_t nout, int64_t nch, int64_t ldp, int real_dtype, void* sum_dev, double scale, void* stream);
 }  // namespace mdsp

@@ -1,4 +1,4 @@
-// Run-time-schedule spectral kernel (round 6; the kernels: compiled by gx_inst_*.hip, launched through gx_run; planned and dispatched by spectral_gx.h inside spectral.hip): Welch / STFT / spectrogram / periodogram for
+// Run-time-schedule spectral kernel (round 6; the kernels: compiled by gx_inst_*.hip, launched through gx_run; planned and dispatched by spectral_gx.h inside welch.hip and stft.hip): Welch / STFT / spectrogram / periodogram for
 // EVERY 7-smooth transform size a workgroup can hold on ONE LDS buffer -- up to 16384 points Float32 / ComplexF32 (128 KiB + group padding), 8192
 // Float64 / ComplexF64 -- and, with a fused column step in front, for nfft = R0 x S up to R0 = 32.  It closes the gap between the compile-time
 // schedules of spectral_gen.h (23 sizes up to 8000 / 8192) and the multi-pass engine of bigfft.hip: welch_pgram(s) / periodogram / spectrogram / stft

@@ -1,5 +1,5 @@
 // Host-pointer entry points (mdsp_ols_exec_host, mdsp_welch_exec_host; mdsp_stft_exec_host and mdsp_fir_exec_host live next to their plans in
-// spectral.hip / fir.hip): the reference's own call shape -- every DSP.jl entry takes host Arrays (Filters/filt.jl:458-476,
+// stft.hip / fir.hip): the reference's own call shape -- every DSP.jl entry takes host Arrays (Filters/filt.jl:458-476,
 // periodograms.jl:647-744) -- on the chunked three-stage pipeline of hostpipe.h: one stream per PCIe direction plus one for the kernels, three
 // lanes of buffers, so that chunk k's D2H, chunk k+1's kernels and chunk k+2's H2D are in flight together.
 // Callers whose arrays are ALREADY page-locked (mdsp_host_alloc / mdsp_host_register) pass MDSP_HOST_PINNED and skip the staging

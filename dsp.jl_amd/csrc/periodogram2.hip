@@ -1,5 +1,5 @@
 // 2-D periodogram: periodogram(s::AbstractMatrix{<:Real}; nfft, fs, radialsum, radialavg) (periodograms.jl:473-509) with the
-// kernels fft2pow2! / fft2pow2radial! (:175-232), composed from the single-column STFT plans of spectral.hip and three kernels of
+// kernels fft2pow2! / fft2pow2radial! (:175-232), composed from the single-column STFT plans of stft.hip and three kernels of
 // its own.  An exec is four steps on the caller's stream, with no host synchronisation:
 //
 //   1. rows     -- internal STFT plan (n = n1, noverlap 0, nfft = N1, one-sided, raw columns) over the n2 columns of s:

@@ -1,4 +1,4 @@
-// Mixed-radix fused spectral kernel (included by spectral.hip inside its anonymous namespace): Welch / STFT / spectrogram / periodogram for
+// Mixed-radix fused spectral kernel (included by spectral_gen.hip, spectral.hip and spectral_ct*.hip inside their anonymous namespaces): Welch / STFT / spectrogram / periodogram for
 // the transform sizes nextfastfft (util.jl:134) produces besides powers of two -- 2^a 3^b 5^c 7^d, e.g. 1000, 1536, 3000 -- which DSP.jl
 // uses by default (nfft = nextfastfft(n): periodograms.jl:393, :560, :872).  One persistent kernel:
 //

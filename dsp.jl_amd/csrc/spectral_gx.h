@@ -1,4 +1,4 @@
-// Host side of the run-time-schedule spectral kernel (gx_kernels.h; included by spectral.hip inside its anonymous namespace): which sizes it takes, the
+// Host side of the run-time-schedule spectral kernel (gx_kernels.h; included by spectral.hip, welch.hip and stft.hip inside their anonymous namespaces): which sizes it takes, the
 // split nfft = R0 x S, root tables, launch geometry.  The kernels themselves live in their own translation units (gx_inst_*.hip) behind mdsp::gx_run.
 #pragma once
 
@@ -44,23 +44,7 @@ inline bool gx_choose(int dtype, int64_t nfft, bool welch, int* R0_out, mdsp::gx
     }
     return found;
 }
-// the column factor of the split (1: one workgroup per transform; 0: no schedule), memoised per size and precision (plan creation and the plan cache's
-// key ask for it; the schedule search behind it plans every candidate split)
-inline int gx_split_r0(int dtype, int64_t nfft) {
-    static std::mutex mu;
-    static std::map<int64_t, int> memo;   // (nfft << 1 | double) -> R0
-    const int64_t key = (nfft << 1) | (dtype_is_double(dtype) ? 1 : 0);
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        if (auto it = memo.find(key); it != memo.end()) return it->second;
-    }
-    int R0 = 0;
-    if (!gx_choose(dtype, nfft, true, &R0, nullptr)) R0 = 0;
-    std::lock_guard<std::mutex> lk(mu);
-    memo.emplace(key, R0);
-    return R0;
-}
-inline bool gx_size_ok(int dtype, int64_t nfft) { return gx_split_r0(dtype, nfft) > 0; }
+// (the memoised answer for the routing -- gx_split_r0, gx_size_ok -- is spectral.hip's: one memo per process)
 
 // at plan creation: the schedule, the split and the twiddle tables
 template <typename R> int gx_prepare(GxPlan& gp, int dtype, int64_t nfft, bool welch) {

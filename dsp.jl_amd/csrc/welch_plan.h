@@ -1,4 +1,4 @@
-// The Welch plan object (opaque behind the C ABI), shared by spectral.hip (kernels), comm.hip (all-reduce of its accumulators)
+// The Welch plan object (opaque behind the C ABI), shared by welch.hip (kernels), comm.hip (all-reduce of its accumulators)
 // and hostpath.hip (host-pointer pipeline).
 #pragma once
 
@@ -28,10 +28,10 @@ struct mdsp_welch_plan_s {
     // after mdsp_welch_allreduce the frame count summed over ranks lives on the DEVICE (kdev, one double, reduced together with the sums: no host
     // round trip, no stream synchronisation); mdsp_welch_finalize(plan, 0, ...) reads it there.  acc_frames stays this rank's own count.
     mdsp::DevBuf kdev;
-    mdsp::DevBuf redtmp;         // group sums of the two-step slice reduction (reduce_partials, spectral.hip)
+    mdsp::DevBuf redtmp;         // group sums of the two-step slice reduction (reduce_partials, welch.hip)
     mdsp::big::EngineHolder big;   // nfft above the single-workgroup kernels: the multi-pass engine (bigfft.hip), built at the first accumulate
     mdsp::GxPlan gx;             // 7-smooth sizes without a compile-time schedule, up to 32 x 16384 points: the run-time-schedule kernel (spectral_gx.h)
-    // (the tables of the plan's route -- table, winr, gx, ctrows, ctcols, w64prep -- are built at its creation: spectral.hip prepare_welch_tables)
+    // (the tables of the plan's route -- table, winr, gx, ctrows, ctcols, w64prep -- are built at its creation: welch.hip prepare_welch_tables)
     mdsp::DevBuf winr;           // lean compile-time schedules (CtSched flag 4096): the window in the working precision, nfft values, zero tail
     mdsp::CtRowsPlan ctrows;     // ... or R0 x S in two kernels from R0 = 5 (spectral_ctrows.hip)
     mdsp::CtColsPlan ctcols;     // ... and those that are R0 x a compile-time row schedule (spectral_ctcols.hip)

@@ -8,12 +8,12 @@ the prefetching form of ols_fused_kernel.  With MDSP_WG_PER_CU=1 and two channel
 units give every slot a run of three; this module works out how many, from the same arithmetic the host uses.
 
 What is mirrored (dsp.jl_amd/csrc):
-    geometry   spectral.hip `template <typename R, int N> struct Geo` (EMAX / E / T / G), welch_launch_n (the half-frame kernels' EH / GH and the real
+    geometry   spectral_op.h `template <typename R, int N> struct Geo` (EMAX / E / T / G), welch.hip welch_launch_n (the half-frame kernels' EH / GH and the real
                Float32 nfft 4096 launch with 16 elements per thread), ols.hip launch_fused_n (EMAX / E / T / G, one transform per workgroup for real
                Float32 nfft 2048), common.h slots_per_workgroup
-    schedule   spectral.hip set_schedule, ols.hip launch_fused_geo (the same two lines)
-    slots      spectral.hip grid_for (the channels SHARE the resident workgroups: grid.y = channels), ols.hip launch_fused_geo (units span the columns)
-    carry_shift  spectral.hip stft_launch_n / welch_launch_n: `shift = (n == N && hop % T == 0 && hop / T < E) ? hop / T : 0` and the instantiated SHIFTs
+    schedule   spectral_op.h set_schedule, ols.hip launch_fused_geo (the same two lines)
+    slots      spectral_op.h grid_for (the channels SHARE the resident workgroups: grid.y = channels), ols.hip launch_fused_geo (units span the columns)
+    carry_shift  stft.hip stft_launch_n / welch.hip welch_launch_n: `shift = (n == N && hop % T == 0 && hop / T < E) ? hop / T : 0` and the instantiated SHIFTs
 
 tests/test_run_schedule_cases_cpu.py holds these tables to the properties the GPU tests rely on, for several CU counts: a change of a geometry that
 would quietly turn a case back into run_len == 1, or a SHIFT case into the generic kernel, fails there.
@@ -47,7 +47,7 @@ def slots_per_workgroup(T):
 def geometry(kind, dtype, nfft):
     """(E, T, G): elements per thread, threads per transform, transforms (slots) per workgroup.
 
-    kind  "stft"        stft_fused_kernel, stft_pair_kernel: Geo<R, N> (spectral.hip stft_launch_n)
+    kind  "stft"        stft_fused_kernel, stft_pair_kernel: Geo<R, N> (stft.hip stft_launch_n)
           "welch"       welch_fused_kernel: Geo<R, N>, except real Float32 nfft 4096, launched with E = 16, G = 1 (welch_launch_n, "the headline shape
                         off the half-frame path")
           "welch_half"  welch_half_kernel / welch_half3_kernel (real, n == nfft, hop == n/2): EH = 16 for Float32 nfft >= 2048, else Geo's E
@@ -79,7 +79,7 @@ def geometry(kind, dtype, nfft):
 
 
 def schedule(nunits, slots, runs=1):
-    """(run_len, niter) as set_schedule (spectral.hip) and launch_fused_geo (ols.hip) write them:
+    """(run_len, niter) as set_schedule (spectral_op.h) and launch_fused_geo (ols.hip) write them:
         run_len = max(1, cdiv(nunits, nslots * runs));  niter = cdiv(cdiv(nunits, run_len), nslots) * run_len
     Slot s walks the runs s, s + nslots, s + 2 nslots, ...; run g covers the units [g run_len, (g + 1) run_len)."""
     run_len = max(1, _cdiv(nunits, slots * runs))
@@ -125,7 +125,7 @@ def runs_of_slot(nunits, nslots, runs, s):
     return out
 
 
-# the SHIFTs stft_launch_n / welch_launch_n instantiate (spectral.hip): 1, 2, 4 where E > 4, and for the STFT 8 where E > 8 (nfft 1024)
+# the SHIFTs stft_launch_n / welch_launch_n instantiate (stft.hip, welch.hip): 1, 2, 4 where E > 4, and for the STFT 8 where E > 8 (nfft 1024)
 def _instantiated_shifts(op, E):
     if E <= 4:
         return ()

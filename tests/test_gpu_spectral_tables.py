@@ -107,7 +107,7 @@ def test_prepared_block_of_the_nfft_4096_kernel(d):
     import torch
     assert _route(ct.WELCH, ct.F32, 4096) == 1
     cu = torch.cuda.get_device_properties(0).multi_processor_count
-    K = 16 * cu                            # K / 2 = 8 units per CU: the hand-allocated kernel (spectral.hip welch_launch_n)
+    K = 16 * cu                            # K / 2 = 8 units per CU: the hand-allocated kernel (welch.hip welch_launch_n)
     length = (K - 1) * 2048 + 4096
     g = torch.Generator(device="cuda")
     g.manual_seed(4096)

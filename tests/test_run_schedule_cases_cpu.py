@@ -48,7 +48,7 @@ def test_schedule_is_the_hosts_formula():
 
 def test_geometry_mirrors_the_launchers():
     g = rs.geometry
-    # Geo<R, N> (spectral.hip): 8 elements per thread, 16 at Float32 nfft 1024, whole wavefronts; several one-wave transforms share a workgroup
+    # Geo<R, N> (spectral_op.h): 8 elements per thread, 16 at Float32 nfft 1024, whole wavefronts; several one-wave transforms share a workgroup
     assert [g("stft", rs.C32, n) for n in (256, 512, 1024, 2048, 4096, 8192)] == [(4, 64, 4), (8, 64, 4), (16, 64, 4), (8, 256, 1), (8, 512, 1), (8, 1024, 1)]
     assert [g("stft", rs.F64, n) for n in (256, 512, 1024, 2048, 4096)] == [(4, 64, 4), (8, 64, 4), (8, 128, 1), (8, 256, 1), (8, 512, 1)]
     assert g("welch", rs.C32, 4096) == (8, 512, 1) and g("welch", rs.F32, 4096) == (16, 256, 1) and g("welch", rs.F64, 4096) == (8, 512, 1)

@@ -9,7 +9,7 @@ wave for 64 complex points (128) + 64 power accumulators + 28 twiddle values + t
 their last use, which the script knows because it emits the dataflow itself.
 
 What it writes:  dsp.jl_amd/csrc/welch_w64_asm.s  (assembled by build.py with clang -x assembler, linked by ld.lld, loaded with
-hipModuleLoadData by csrc/welch_w64.h (included by spectral.hip)).  `--check` runs the emitted instruction list through a lane-level emulator of the ~15 opcodes it
+hipModuleLoadData by csrc/welch_w64.h (included by welch.hip)).  `--check` runs the emitted instruction list through a lane-level emulator of the ~15 opcodes it
 uses (numpy, one wavefront) for two consecutive units and compares the accumulators with numpy's FFT of the windowed frame pairs.
 
 Kernel contract (welch_run_w64asm in csrc/welch_w64.h fills the arguments):
