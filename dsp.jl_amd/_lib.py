@@ -27,6 +27,7 @@ RESP_DERIV, RESP_NEG = 1, 2
 RESP_COMPLEX, RESP_ANGLE, RESP_REAL_MINUS = 0, 1, 2
 RESP_W, RESP_POINTS = 0, 1
 SHIFT_AUTO, SHIFT_DISJOINT, SHIFT_HALO, SHIFT_STAGED = 0, 1, 2, 3
+CHUNK_ROCFFT_WELCH, CHUNK_ROCFFT_STFT, CHUNK_ROCFFT_OLS, CHUNK_HILBERT, CHUNK_BIG_SPECTRAL, CHUNK_BIG_OLS, CHUNK_BIG_OLS_ROWS = range(7)
 HOST_PINNED = 1
 COMM_ID_BYTES = 128
 
@@ -121,6 +122,7 @@ PROTOTYPES = {
     "mdsp_stft_exec": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, vp]),
     "mdsp_stft_exec_host": (ci, [vp, vp, i64, i64, i64, vp, i64, i64, ci]),
     "mdsp_spectral_route_for": (ci, [ci, ci, i64, ci, pint, pint, pint]),
+    "mdsp_chunk_units_for": (ci, [ci, ci, i64, i64, pi64]),
     "mdsp_hilbert": (ci, [vp, i64, i64, i64, ci, vp, i64, vp]),
     "mdsp_periodogram2_plan_create": (ci, [pvp, i64, i64, i64, i64, cd, ci, ci, ci]),
     "mdsp_periodogram2_plan_destroy": (ci, [vp]),

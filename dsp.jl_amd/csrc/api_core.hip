@@ -2,6 +2,7 @@
 #include <atomic>
 #include <cmath>
 
+#include "chunk_units.h"
 #include "common.h"
 #include "hostpipe.h"
 
@@ -400,6 +401,31 @@ int64_t mdsp_optimal_fft_len(int64_t nb, int64_t nx) {
 int64_t mdsp_frame_count(int64_t len, int64_t n, int64_t noverlap) {
     if (n <= 0 || noverlap < 0 || noverlap >= n) return -1;
     return len >= n ? (len - n) / (n - noverlap) + 1 : 0;
+}
+
+// The chunk of an engine loop that cuts its work to a memory budget (chunk_units.h: the functions the loops themselves call)
+int mdsp_chunk_units_for(int kind, int dtype, int64_t n, int64_t units, int64_t* units_per_chunk) {
+    if (!dtype_valid(dtype)) MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid dtype %d", dtype);
+    if (n < 1 || units < 0) MDSP_FAIL(MDSP_ERR_ARGUMENT, "n (%lld) must be >= 1 and units (%lld) >= 0", (long long)n, (long long)units);
+    const bool cplx = dtype_is_complex(dtype);
+    const int64_t rsz = dtype_is_double(dtype) ? 8 : 4;
+    const int64_t rocfft_budget = (int64_t)tunables().rocfft_chunk_mib << 20, big_budget = (int64_t)tunables().big_chunk_mib << 20;
+    int64_t c = 0;
+    switch (kind) {
+        case MDSP_CHUNK_ROCFFT_WELCH:
+        case MDSP_CHUNK_ROCFFT_STFT: c = chunk_units_rocfft_spectral(cplx, rsz, n, units, rocfft_budget); break;
+        case MDSP_CHUNK_ROCFFT_OLS: c = chunk_units_rocfft_ols(cplx, rsz, n, units); break;
+        case MDSP_CHUNK_HILBERT:
+            if (cplx) MDSP_FAIL(MDSP_ERR_ARGUMENT, "hilbert is defined for real signals");
+            c = chunk_units_hilbert(rsz, n, units);
+            break;
+        case MDSP_CHUNK_BIG_SPECTRAL:
+        case MDSP_CHUNK_BIG_OLS_ROWS: c = chunk_units_big(rsz, n, units, big_budget, 1); break;
+        case MDSP_CHUNK_BIG_OLS: c = chunk_units_big(rsz, n, units, big_budget, 2); break;
+        default: MDSP_FAIL(MDSP_ERR_ARGUMENT, "invalid kind %d", kind);
+    }
+    if (units_per_chunk) *units_per_chunk = c;
+    return MDSP_OK;
 }
 
 // stream_filt.jl:317-322: ceil(((inputlength*L) - phi + 1) / M)

@@ -22,6 +22,7 @@
 
 #include "bigfft.h"
 #include "bigfft_plan.h"
+#include "chunk_units.h"
 #include "welch_plan.h"
 
 using namespace mdsp;
@@ -636,7 +637,7 @@ int run(Engine* e, int mode, const void* s, int64_t K, int64_t hop, const double
         }
     }
     const int64_t per = (int64_t)sizeof(cx<R>) * N;
-    const int64_t C = std::max<int64_t>(1, std::min<int64_t>(units, ((int64_t)tunables().big_chunk_mib << 20) / per));
+    const int64_t C = chunk_units_big((int64_t)sizeof(R), N, units, (int64_t)tunables().big_chunk_mib << 20, 1);
     MDSP_TRY(e->work.reserve((size_t)(per * C)));
     const bool untangle = mode == 1 && !CPLX;
     if (untangle) MDSP_TRY(e->nat.reserve((size_t)(per * C)));
@@ -709,7 +710,7 @@ template <typename R> int run_ols(Engine* e, bool cplx, const void* x, int64_t n
     const int64_t u0 = cplx ? g0 : g0 / 2, u1 = cplx ? g1 : cdiv(g1, 2);
     if (u1 <= u0) return MDSP_OK;
     const int64_t per = (int64_t)sizeof(cx<R>) * N;
-    const int64_t C = std::max<int64_t>(1, std::min<int64_t>(u1 - u0, ((int64_t)tunables().big_chunk_mib << 20) / (2 * per)));
+    const int64_t C = chunk_units_big((int64_t)sizeof(R), N, u1 - u0, (int64_t)tunables().big_chunk_mib << 20, 2);
     MDSP_TRY(e->work.reserve((size_t)(per * C)));
     MDSP_TRY(e->nat.reserve((size_t)(per * C)));
     const int cus = device_cu_count();
@@ -760,7 +761,7 @@ template <typename R> int run_ols_rows(Engine* e, bool cplx, const void* x, int6
     const int64_t u0 = cplx ? g0 : g0 / 2, u1 = cplx ? g1 : cdiv(g1, 2);
     if (u1 <= u0) return MDSP_OK;
     const int64_t per = (int64_t)sizeof(cx<R>) * N;
-    const int64_t C = std::max<int64_t>(1, std::min<int64_t>(u1 - u0, ((int64_t)tunables().big_chunk_mib << 20) / per));
+    const int64_t C = chunk_units_big((int64_t)sizeof(R), N, u1 - u0, (int64_t)tunables().big_chunk_mib << 20, 1);
     MDSP_TRY(e->work.reserve((size_t)(per * C)));
     const int cus = device_cu_count();
     for (int64_t c0 = u0; c0 < u1; c0 += C) {
@@ -842,7 +843,7 @@ int run_welch_rows(Engine* e, const void* s, int64_t K, int64_t hop, const doubl
     }
     MDSP_TRY(mdsp_welch_reset(e->rowplan));
     const int64_t per = (int64_t)sizeof(cx<R>) * N;
-    const int64_t C = std::max<int64_t>(1, std::min<int64_t>(units, ((int64_t)tunables().big_chunk_mib << 20) / per));
+    const int64_t C = chunk_units_big((int64_t)sizeof(R), N, units, (int64_t)tunables().big_chunk_mib << 20, 1);
     MDSP_TRY(e->work.reserve((size_t)(per * C)));
     const int cus = device_cu_count();
     for (int64_t c0 = 0; c0 < units; c0 += C) {

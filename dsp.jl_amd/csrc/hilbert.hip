@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <mutex>
 
+#include "chunk_units.h"
 #include "common.h"
 #include "fft_lds.h"   // cx
 #include "rocfft_wrap.h"
@@ -58,8 +59,7 @@ HilbertCache& hilbert_cache(bool dbl) {
 template <typename R> int hilbert_run(const void* x, int64_t n, int64_t ncols, int64_t ldx, void* out, int64_t ldo, hipStream_t st) {
     const int64_t nspec = n / 2 + 1;
     // columns are processed in batches whose intermediates stay within ~256 MiB
-    const int64_t per_col = (int64_t)sizeof(R) * n + (int64_t)sizeof(cx<R>) * (nspec + n);
-    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(ncols, (int64_t(256) << 20) / per_col));
+    const int64_t batch = chunk_units_hilbert((int64_t)sizeof(R), n, ncols);
     HilbertCache& hc = hilbert_cache(sizeof(R) == 8);
     std::lock_guard<std::mutex> lk(hc.mu);
     if (hc.used && hc.last != st) MDSP_HIP(hipStreamSynchronize(hc.last));

@@ -29,6 +29,7 @@
 #define MDSP_FFT_SGPR_CONST 0
 #endif
 
+#include "chunk_units.h"
 #include "common.h"
 #include "devio.h"
 #include "fft_lds.h"
@@ -1051,8 +1052,7 @@ int exec_rocfft(mdsp_ols_plan_s* pl, const void* x, int64_t nx, int64_t ncols, i
     const int64_t nunits = u_end >= 0 ? std::min(u_end, nblocks * ncols) : nblocks * ncols;   // unit = block (no pair packing in this engine)
     const int64_t nspec = CPLX ? nfft : nfft / 2 + 1;
     // chunk so that td + fd stay cache resident (~64 MiB)
-    const int64_t per_unit = (int64_t)sizeof(T) * nfft + (CPLX ? 0 : (int64_t)sizeof(cx<R>) * nspec);
-    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nblocks * ncols, (int64_t(64) << 20) / per_unit));
+    const int64_t batch = chunk_units_rocfft_ols(CPLX, (int64_t)sizeof(R), nfft, nblocks * ncols);
     if (pl->batch != batch) {
         MDSP_TRY(pl->td.reserve((size_t)(sizeof(T) * nfft * batch)));
         if (!CPLX) MDSP_TRY(pl->fd.reserve((size_t)(sizeof(cx<R>) * nspec * batch)));

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "common.h"
+#include "chunk_units.h"
 #include "rocfft_wrap.h"
 #include "bigfft.h"
 #include "gx_plan.h"

@@ -279,8 +279,7 @@ int welch_accumulate_rocfft(mdsp_welch_plan_s* pl, const void* s, int64_t len, i
         pl->acc_fresh = false;
     }
     if (nunits > 0) {
-        const int64_t per_unit = (int64_t)sizeof(TT) * nfft + (int64_t)sizeof(cx<R>) * nspec;
-        const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(nunits, rocfft_chunk_bytes() / per_unit));
+        const int64_t batch = chunk_units_rocfft_spectral(CPLX, (int64_t)sizeof(R), nfft, nunits, rocfft_chunk_bytes());
         if (pl->batch != batch) {
             MDSP_TRY(pl->fr.reserve((size_t)(sizeof(TT) * nfft * batch)));
             MDSP_TRY(pl->spec.reserve((size_t)(sizeof(cx<R>) * nspec * batch)));

@@ -297,6 +297,23 @@ enum {
  * column factor r0 of the CTCOLS* / CTROWS routes (0 otherwise).  Fails with the status and message plan creation would.  Any output pointer may be NULL. */
 int mdsp_spectral_route_for(int kind, int dtype, int64_t nfft, int engine, int* engine_used, int* route, int* r0);
 
+/* The engine loops that cut their work into chunks so that the intermediates stay within a memory budget */
+enum {
+    MDSP_CHUNK_ROCFFT_WELCH = 0, /* rocFFT Welch: a unit is a frame of a channel, n = nfft; budget MDSP_ROCFFT_CHUNK_MIB (default 192) */
+    MDSP_CHUNK_ROCFFT_STFT = 1,  /* rocFFT STFT / spectrogram / periodogram / multitaper: the same */
+    MDSP_CHUNK_ROCFFT_OLS = 2,   /* rocFFT overlap-save: a unit is a block of a column, n = nfft; 64 MiB */
+    MDSP_CHUNK_HILBERT = 3,      /* hilbert: a unit is a column of n points (real dtypes); 256 MiB */
+    MDSP_CHUNK_BIG_SPECTRAL = 4, /* multi-pass engine, Welch sums (three passes or the rows form) and columns: a unit is a transform of n = nfft points -- two real
+                                    frames, one complex frame; budget MDSP_BIG_CHUNK_MIB (default 1024) */
+    MDSP_CHUNK_BIG_OLS = 5,      /* multi-pass overlap-save on natural-order spectra: a unit is a transform of n = exec_nfft points (two real blocks, one complex
+                                    block) and takes two buffers of the same budget */
+    MDSP_CHUNK_BIG_OLS_ROWS = 6  /* multi-pass overlap-save in the rows form: one buffer */
+};
+/* Pure host arithmetic, no device needed (like mdsp_ols_geometry_for): how many of `units` units the loop `kind` (MDSP_CHUNK_*) takes per chunk under the
+ * current tunables -- the value the loop itself computes, at least 1 and at most max(units, 1); the loop then runs ceil(units / *units_per_chunk) chunks, the
+ * last one with what is left.  dtype: the signal's.  units_per_chunk may be NULL. */
+int mdsp_chunk_units_for(int kind, int dtype, int64_t n, int64_t units, int64_t* units_per_chunk);
+
 /* ------------------------------------------------------------------------------------------------------
  * 2-D periodogram (periodograms.jl:473-509, kernels fft2pow2! / fft2pow2radial! :175-232)
  *   periodogram(s::AbstractMatrix{<:Real}; nfft = (nfft1, nfft2), fs, radialsum, radialavg) of a real (n1, n2) matrix:

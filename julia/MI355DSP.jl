@@ -1220,6 +1220,12 @@ function spectral_route_for(kind::Integer, ::Type{T}, nfft::Integer, engine::Int
     check(ccall((:mdsp_spectral_route_for, lib), Cint, (Cint, Cint, Int64, Cint, Ref{Cint}, Ref{Cint}, Ref{Cint}), kind, mdtype(T), nfft, engine, eng, route, r0))
     (engine = Int(eng[]), route = Int(route[]), r0 = Int(r0[]))
 end
+# how many of `units` units the chunked engine loop `kind` (MDSP_CHUNK_* of include/mi355dsp.h) takes per chunk under the current tunables; no device
+function chunk_units_for(kind::Integer, ::Type{T}, n::Integer, units::Integer) where {T}
+    c = Ref{Int64}(0)
+    check(ccall((:mdsp_chunk_units_for, lib), Cint, (Cint, Cint, Int64, Int64, Ref{Int64}), kind, mdtype(T), n, units, c))
+    Int(c[])
+end
 function stft(s::Union{AbstractVecOrMat{T},DeviceArray{T}}, n::Int=size(s, 1) >> 3, noverlap::Int=n >> 1, psdonly::Bool=false;
               onesided::Bool=T <: Real, nfft::Int=nextfastfft(n), fs::Real=1, window=nothing, engine=ENGINE_AUTO, pinned::Bool=false) where {T}
     onesided && T <: Complex && throw(ArgumentError("cannot compute one-sided FFT of a complex signal"))

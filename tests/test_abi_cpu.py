@@ -95,6 +95,19 @@ def test_ols_block_geometry_matches_reference_table():
             _lib.check(lib.mdsp_ols_block_geometry(nb, nx, nfft, len(rows), None, None, None, None, None))
 
 
+def test_chunk_units_without_a_device():
+    """mdsp_chunk_units_for: the chunk of every engine loop that cuts its work to a memory budget, as pure host arithmetic (the functions of
+    csrc/chunk_units.h, which the loops call).  Declared, exported, bound in both hosts; tests/test_chunk_cases_cpu.py holds the values."""
+    hdr = open(os.path.join(ROOT, "include", "mi355dsp.h")).read()
+    jl = open(os.path.join(ROOT, "julia", "MI355DSP.jl")).read()
+    assert "int mdsp_chunk_units_for(int kind, int dtype, int64_t n, int64_t units, int64_t* units_per_chunk);" in hdr
+    assert [int(v) for v in re.findall(r"MDSP_CHUNK_[A-Z_]+ = (\d)", hdr)] == list(range(7))
+    assert ":mdsp_chunk_units_for" in jl and "mdsp_chunk_units_for" in _lib.PROTOTYPES
+    c = C.c_int64()
+    _lib.check(_lib.lib().mdsp_chunk_units_for(_lib.CHUNK_ROCFFT_OLS, _lib.F32, 64, 1 << 30, C.byref(c)))
+    assert c.value == (64 << 20) // (4 * 64 + 8 * 33)            # 129055 blocks of 64 points per 64 MiB
+
+
 def test_overlap_save_plan_choice_without_a_device():
     """mdsp_ols_geometry_for: what mdsp_ols_plan_create would execute, as pure host arithmetic.  The reference's nfft runs as it is up to the largest
     in-LDS transform (8192 Float32 / 4096 Float64), longer filters are re-blocked (one block, then 2 .. 4 partitions), and beyond 16384 / 8192 taps the
