@@ -15,6 +15,9 @@ from . import windows, design  # noqa: F401
 from .windows import (hanning, hann, hamming, rect, bartlett, cosine, blackman, kaiser, dpss, dpsseig, tukey, lanczos, triang,  # noqa: F401
                       gaussian, bartlett_hann, blackmanharris, nuttall, flattop)
 from .design import resample_filter, kaiserord  # noqa: F401
+from .design import (Butterworth, Chebyshev1, Chebyshev2, Elliptic, FilterType, Lowpass, Highpass, Bandpass, Bandstop, ComplexBandpass,  # noqa: F401
+                     FIRWindow, analogfilter, bilinear, prewarp, digitalfilter, iirnotch, transform_prototype, normalize_freq,
+                     normalize_complex_freq)
 from .dspbase import conv, conv_, conv_separable, xcorr, hilbert, optimalfftfiltlength, os_fft_complexity, SMALL_FILT_CUTOFF  # noqa: F401
 from .dspbase import filt as _filt_ba, filt_ as _filt_ba_
 from .filters import (FIRFilter, fftfilt, fftfilt_, tdfilt, tdfilt_, resample, inputlength, outputlength,  # noqa: F401

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _dev, _lib, _plancache, coefficients, design, dspbase, util
 from ._lib import ArgumentError, DimensionMismatch, DomainError, UnsupportedError
-from .coefficients import Biquad, FilterCoefficients, PolynomialRatio, SecondOrderSections, ZeroPoleGain
+from .coefficients import Biquad, FilterCoefficients, PolynomialRatio, SecondOrderSections, ZeroPoleGain, require_z
 from .dspbase import SMALL_FILT_CUTOFF, OlsPlan, _cast_result, _compute_dtype, _host_vec, optimalfftfiltlength
 
 _REAL_KINDS = "fiub"
@@ -115,6 +115,7 @@ def filt_(out, b, x):
     """``filt!(out, b, x)`` (filt.jl:530-533); ``filt!(out, f, x)`` for coefficient objects (:53-62, :82-89) and for a ``DF2TFilter`` built from one."""
     if isinstance(b, DF2TFilter):
         return b.filt_(out, x)
+    require_z(b, "filt!")
     if isinstance(b, FilterCoefficients) and not isinstance(b, PolynomialRatio):
         if tuple(out.shape) != tuple(x.shape):
             raise DimensionMismatch("out size must match x")              # :54, :83
@@ -218,6 +219,7 @@ def _own_columns(x, W):
 
 def _filt_coef(f, x):
     """``filt(f, x)`` for Biquad / SecondOrderSections / ZeroPoleGain (filt.jl:64-65, :91-92, :95); PolynomialRatio: ``filt(b, a, x)`` (:30)."""
+    require_z(f, "filt")
     if isinstance(f, PolynomialRatio):
         return dspbase.filt(f.b, f.a, x)
     table, gain, T, G = _as_sections(f)
@@ -565,6 +567,7 @@ class DF2TFilter:
 
     def __init__(self, b, a=1.0, dtype=None, coldims=()):
         self._sections = None
+        require_z(b, "DF2TFilter")
         if isinstance(b, PolynomialRatio):                              # DF2TFilter(coef::PolynomialRatio, ...): the vector form below
             b, a = b.b, b.a
         elif isinstance(b, FilterCoefficients):                         # filt.jl:184-186, :198-200, :227-230
@@ -678,6 +681,7 @@ def filtfilt(b, *args):
     """``filtfilt(b, x)`` / ``filtfilt(b, a, x)`` with scalar or length-1 ``a`` (filt.jl:301-338): zero-phase FIR
     filtering -- odd-symmetric extension by ``length(b)-1`` samples, one pass with ``conv(b, reverse(b))``, trim.  ``b`` real or complex."""
     if isinstance(b, FilterCoefficients) and len(args) == 1:
+        require_z(b, "filtfilt")
         if isinstance(b, PolynomialRatio):                              # filt.jl:364
             return filtfilt(b.b, b.a, args[0])
         return _filtfilt_sections(b, args[0])                           # :341, :363

@@ -1,5 +1,5 @@
 """Filter responses of DSP.jl ``src/Filters/response.jl`` on the device (``mdsp_resp_*``): ``freqresp``, ``phaseresp``, ``grpdelay``, ``impresp``, ``stepresp``
-for ``:z``-domain filters with real coefficients.
+for filters with real coefficients; ``freqresp``, ``phaseresp`` and ``grpdelay`` also of analog (``"s"``) filters, at the points ``i w`` (response.jl:35, :113-120).
 
 Every coefficient type runs through its own form -- a ``PolynomialRatio`` through POLY, a ``Biquad`` / ``SecondOrderSections`` through SECTIONS, a
 ``ZeroPoleGain`` through ZPK (response.jl:42-52) --, never through a conversion.  The working type is ComplexF32 when the coefficients and ``w`` are both
@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _dev, _lib, _plancache
 from ._lib import ArgumentError, UnsupportedError
-from .coefficients import Biquad, FilterCoefficients, PolynomialRatio, SecondOrderSections, ZeroPoleGain, coefa, coefb
+from .coefficients import Biquad, FilterCoefficients, PolynomialRatio, SecondOrderSections, ZeroPoleGain, coefa, coefb, require_z
 from .unwrap import unwrap
 
 _F32, _F64 = np.dtype(np.float32), np.dtype(np.float64)
@@ -71,8 +71,24 @@ def resp_geometry(form: int, dtype, ncoef: int, has_den: bool, nw: int, chunks: 
     return c.value, ln.value, ws.value
 
 
-def _freqrange():
-    return np.linspace(0.0, np.pi, 257)                                  # response.jl:158
+def _freqrange(f=None):
+    if f is None or f.domain == "z":
+        return np.linspace(0.0, np.pi, 257)                              # response.jl:158
+    f = ZeroPoleGain(f)                                                  # :159-175, on the host
+    w_interesting = np.sort(np.abs(np.concatenate([f.p, f.z])).astype(np.float64))
+    include_zero = w_interesting.size > 0 and w_interesting[0] == 0
+    nonzero = np.flatnonzero(w_interesting)
+    if nonzero.size == 0:                                                # no non-zero poles or zeros
+        with np.errstate(divide="ignore"):
+            inv_k = np.float64(1.0) / np.float64(f.k)
+        if not include_zero or not np.isfinite(inv_k):
+            w = 10.0 ** np.arange(-1, 7)                                 # fallback
+            w[0] = 0.0
+            return w
+        return np.linspace(0.0, 10 * float(max(np.float64(f.k), inv_k)), 200)   # the point where |H| = 1 (if any), and further by a factor 10
+    w_min, w_max = w_interesting[nonzero[0]], w_interesting[-1]          # from the smallest to the largest pole / zero, extended by a factor 10
+    w = 10.0 ** np.linspace(np.log10(w_min) - 1, np.log10(w_max) + 1, 200)
+    return np.concatenate([[0.0], w]) if include_zero else w
 
 
 def _check_filter(f):
@@ -98,8 +114,17 @@ def _real_type(wdt, *coef_types):
     return _F32 if single else _F64
 
 
+def _in_mode(f):
+    """The plan's input: ``w`` for a digital filter (the kernel forms e^{iw}), the points ``i w`` for an analog one (response.jl:27, :35)."""
+    return _lib.RESP_POINTS if f.domain == "s" else _lib.RESP_W
+
+
 def _form_of(f, wdt):
-    """(form, real type, num, den, gain, flags) of a filter's own form."""
+    """(form, real type, num, den, gain, flags) of a filter's own form.  The section and zero-pole-gain forms are written in the point itself, so they
+    serve both domains; an ``"s"`` ``PolynomialRatio`` hands its coefficients over lowest power first, to be evaluated at the point as it is."""
+    if isinstance(f, PolynomialRatio) and f.domain == "s":
+        den = None if len(f.a) == 1 and f.a[0] == 1 else f.a[::-1].copy()
+        return _lib.RESP_POLY, _real_type(wdt, f.dtype), f.b[::-1].copy(), den, 1.0, 0
     if isinstance(f, PolynomialRatio):
         return _lib.RESP_POLY, _real_type(wdt, f.dtype), f.b, (f.a if len(f.a) > 1 else None), 1.0, _lib.RESP_NEG
     if isinstance(f, Biquad):
@@ -111,8 +136,9 @@ def _form_of(f, wdt):
     raise TypeError("not a filter coefficient object")
 
 
-def _run(w, R, form, num, den, gain, flags, out_mode, cminus=0.0):
-    """One plan over the points of ``w`` (already checked); the result has w's shape and lives where w lives."""
+def _run(w, R, form, num, den, gain, flags, out_mode, cminus=0.0, in_mode=_lib.RESP_W):
+    """One plan over the points of ``w`` (already checked); the result has w's shape and lives where w lives.  ``in_mode`` RESP_POINTS: the plan is given
+    the points ``i w`` of the imaginary axis, formed on the device, instead of ``w``."""
     _lib.require_device()
     shape = tuple(int(k) for k in w.shape)
     nw = int(np.prod(shape, dtype=np.int64))
@@ -121,12 +147,14 @@ def _run(w, R, form, num, den, gain, flags, out_mode, cminus=0.0):
     if nw == 0:                                                          # nothing to do, and no launch
         return _dev.torch.empty(shape, dtype=_dev.torch_dtype(odt), device=w.device) if on_device else np.empty(shape, dtype=odt)
     wd = _dev.as_device(w, R).contiguous().reshape(-1)
+    if in_mode == _lib.RESP_POINTS:                                      # im .* w (response.jl:35, :118)
+        wd = _dev.torch.complex(_dev.torch.zeros_like(wd), wd)
     out = _dev.torch.empty(nw, dtype=_dev.torch_dtype(odt), device=wd.device)
     numa, dena = np.asarray(num), (None if den is None else np.asarray(den))
     key = ("resp", _plancache.ctx_key(), form, R.str, numa.tobytes(), numa.dtype.str, None if dena is None else dena.tobytes(), float(gain), flags, out_mode,
-           float(cminus), nw)
+           float(cminus), nw, in_mode)
     plan = _plancache.plans.get(key, lambda: RespPlan(form, R, numa, numa if den is num and den is not None else dena, gain, nw, flags, out_mode,
-                                                      _lib.RESP_W, cminus))
+                                                      in_mode, cminus))
     plan.exec(_dev.ptr(wd), _dev.ptr(out))
     out = out.reshape(shape)
     return out if on_device else out.cpu().numpy()
@@ -136,22 +164,22 @@ def freqresp(f, w=None):
     """``freqresp(f)`` -> ``(H, w)`` with ``w = range(0, π, 257)``; ``freqresp(f, w)`` -> ``H`` (response.jl:16-27)."""
     _check_filter(f)
     if w is None:
-        w = _freqrange()
+        w = _freqrange(f)
         return freqresp(f, w), w
     w, wdt = _w_type(w)
     form, R, num, den, gain, flags = _form_of(f, wdt)
-    return _run(w, R, form, num, den, gain, flags, _lib.RESP_COMPLEX)
+    return _run(w, R, form, num, den, gain, flags, _lib.RESP_COMPLEX, in_mode=_in_mode(f))
 
 
 def phaseresp(f, w=None):
     """``phaseresp(f[, w])`` (response.jl:62-76): ``unwrap(angle.(freqresp(f, w)); dims=ndims)``, the angle taken in the response kernel."""
     _check_filter(f)
     if w is None:
-        w = _freqrange()
+        w = _freqrange(f)
         return phaseresp(f, w), w
     w, wdt = _w_type(w)
     form, R, num, den, gain, flags = _form_of(f, wdt)
-    phi = _run(w, R, form, num, den, gain, flags, _lib.RESP_ANGLE)
+    phi = _run(w, R, form, num, den, gain, flags, _lib.RESP_ANGLE, in_mode=_in_mode(f))
     if len(phi.shape) == 0 or 0 in tuple(phi.shape):
         return phi
     return unwrap(phi, dims=-1)
@@ -167,16 +195,33 @@ def _is_anti_sym(x):                                                     # respo
     return all(x[i] == -x[len(x) - 1 - i] for i in range(n + 1))
 
 
+def _analog_grpdelay_polys(b, a):
+    """``b' a - a' b`` and ``a b`` (response.jl:115-119) of ``coefb`` / ``coefa`` of an ``"s"`` filter, as plain Float64 polynomial products, lowest
+    power first: what the POLY plan takes."""
+    b, a = np.asarray(b, np.float64)[::-1], np.asarray(a, np.float64)[::-1]
+    bd, ad = b[1:] * np.arange(1, len(b)), a[1:] * np.arange(1, len(a))
+    num = np.zeros(max(len(b) + len(a) - 2, 1))
+    for d, c, sign in ((bd, a, 1.0), (ad, b, -1.0)):
+        if len(d):
+            num[:len(d) + len(c) - 1] += sign * np.convolve(d, c)
+    return num, np.convolve(a, b)
+
+
 def grpdelay(f, w=None):
     """``grpdelay(f[, w])`` (response.jl:85-111): a constant for a linear-phase FIR filter, else ``c = xcorr(b, a)`` on the device and
-    ``real(sum k c[k] y^k / sum c[k] y^k) - (length(a) - 1)`` at ``y = exp(-iw)`` in one plan over the one vector ``c``."""
+    ``real(sum k c[k] y^k / sum c[k] y^k) - (length(a) - 1)`` at ``y = exp(-iw)`` in one plan over the one vector ``c``.
+
+    An analog filter (:113-120): ``real((b' a - a' b)(s) / (a b)(s))`` at ``s = iw``, the two products formed on the host in Float64, one plan."""
     _check_filter(f)
     if w is None:
-        w = _freqrange()
+        w = _freqrange(f)
         return grpdelay(f, w), w
     w, wdt = _w_type(w)
     b, a = coefb(f), coefa(f)
     R = _real_type(wdt, b.dtype, a.dtype)
+    if f.domain == "s":
+        num, den = _analog_grpdelay_polys(b, a)
+        return _run(w, R, _lib.RESP_POLY, num, den, 1.0, 0, _lib.RESP_REAL_MINUS, cminus=0.0, in_mode=_lib.RESP_POINTS)
     if len(a) == 1 and (_is_sym(b) or _is_anti_sym(b)):                  # linear-phase FIR
         _lib.require_device()
         shape = tuple(int(k) for k in w.shape)
@@ -192,6 +237,7 @@ def grpdelay(f, w=None):
 
 def _time_response(f, n, step, device):
     _check_filter(f)
+    require_z(f, "stepresp" if step else "impresp")
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
         raise TypeError("n must be an integer")
     if n < 0:
